@@ -2,7 +2,13 @@
 """Headline benchmark: MeshGraphNet (CylinderFlow, 15 rounds, latent 128) training
 steps/s on MI355X through the HIP engine, plus rollout node*steps/s.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K training steps and prints one JSON line (`value` in
+steps/s, `ms_per_step` = milliseconds of one timed step).  ``--dump-outputs DIR`` writes what the
+last timed step computed -- loss, gradient norm, the clipped parameter gradients and the model state
+after the optimiser step -- as DIR/<name>.npy (rank 0; same arguments, same inputs).  ``--full``
+adds every other record listed below; the --no-* switches narrow a full run.
 
 N > 1 without a torch.distributed environment: this process starts
 ``python -m torch.distributed.run --nproc-per-node N bench.py ...`` itself (before anything touches
@@ -14,7 +20,8 @@ on one batch of 16 synthetic CylinderFlow meshes (BASELINE.json configs[1]; data
 already resident in HBM).  For N>1 every rank steps its own batch of 16 and the
 gradients are all-reduced over RCCL each step (weak scaling; value = N*K/T).
 
-The JSON line also carries
+With --full the JSON line also carries
+  rollout_*           rollout node*steps/s of the same batch,
   roofline            HBM roofline of the edge-update kernel (training mode), timed in situ with HIP
                       events on the launch stream; the bf16-MFMA fraction rides along,
   roofline_scatter    HBM roofline of the segment-sum (scatter-add) kernel at the bench size,
@@ -70,7 +77,46 @@ def parse():
     ap.add_argument("--c4-nodes", type=int, default=1_000_000)
     ap.add_argument("--c4-steps", type=int, default=3)
     ap.add_argument("--c5-nodes", type=int, default=150_000, help="nodes of the 3-D mesh of the configs[4] (Transformer) record")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline too: topology rebuild per step, rollout, in-situ kernel rooflines, "
+                         "the batch1 / shipped_cylinder_json / plate_bf16 / c5 / c4 records and the CPU baseline (the --no-* "
+                         "switches narrow a full run); without it only the timed training steps run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (loss, gradient norm, parameter gradients, model "
+                         "state) as DIR/<name>.npy, float32 / float64, at most 64 MB in all")
     return ap.parse_args()
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(path, eng, loss):
+    """What the last timed training step left for its caller: the loss, the gradient norm the clip saw, every parameter's
+    gradient (clipped, as the optimiser used it) and the model state after the optimiser step.  Arrays are written as float32
+    (float64 where the source is not float32); past DUMP_BUDGET_BYTES in all, each array keeps a fixed, seeded sample of its
+    elements (the same for every run with the same arguments)."""
+    import numpy as np
+
+    arrays = {"loss": loss, "grad_norm": eng.last_grad_norm}
+    for k, v in eng.sim.state_dict().items():
+        arrays["state." + k] = v
+    for k, p in eng.sim.named_parameters():
+        if p.grad is not None:
+            arrays["grad." + k] = p.grad
+    for k, v in arrays.items():
+        t = v.detach().cpu() if torch.is_tensor(v) else torch.as_tensor(v)
+        t = t.float() if t.dtype in (torch.float16, torch.bfloat16) else t
+        arrays[k] = t.numpy().astype(np.float32 if t.dtype == torch.float32 else np.float64, copy=False)
+    total = sum(a.nbytes for a in arrays.values())
+    budget = DUMP_BUDGET_BYTES - 256 * len(arrays)   # room for the .npy headers
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        if total > budget:
+            keep = max(1, a.size * budget // total)
+            if keep < a.size:
+                idx = np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))
+                a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 def maybe_self_launch(args):
@@ -1035,15 +1081,18 @@ def main():
         eng.grad_sync = D.OverlappedGradAllReduce(params=list(eng.sim.parameters()))   # 4 MB buckets reduced while the backward pass runs
     batch = gp.cylinder_batch(args.batch, args.nodes, seed0=rank * args.batch).to(dev)
     N, E = batch.x.shape[0], batch.edge_index.shape[1]
-    # topology prep (CSR by dst + by src): timed on its own, outside the headline's timed region --
-    # the topology of a fixed batch is cached; `topology` below reports what a rebuild per step costs
-    ops.Topology(batch.edge_index, N)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(5):
+    # topology prep (CSR by dst + by src), outside the headline's timed region -- the topology of a fixed
+    # batch is cached; with --full it is timed on its own and `topology` below reports what a rebuild per step costs
+    if args.full:
+        ops.Topology(batch.edge_index, N)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(5):
+            batch.mgn_topology = ops.Topology(batch.edge_index, N)
+        torch.cuda.synchronize()
+        topo_ms = 1e3 * (time.perf_counter() - t0) / 5
+    else:
         batch.mgn_topology = ops.Topology(batch.edge_index, N)
-    torch.cuda.synchronize()
-    topo_ms = 1e3 * (time.perf_counter() - t0) / 5
 
     def barrier():
         if world > 1:
@@ -1077,35 +1126,43 @@ def main():
             use_graph = False
     if not use_graph:
         step = lambda: eng.train_step(batch)  # noqa: E731
+    last_loss = [None]   # what the last timed step returned, for --dump-outputs
+
+    def headline_step():
+        last_loss[0] = step()
+
     for _ in range(args.warmup):
-        step()
-    dt = timed(step, args.steps)
+        headline_step()
+    dt = timed(headline_step, args.steps)
     steps_per_s = world * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, last_loss[0])
 
-    # the reference's shuffled loader hands over a NEW 16-mesh union every step: same step with the
-    # topology rebuilt inside it (mgn_topology_build_async: queued without a host synchronisation)
-    def step_rebuild():
-        batch.mgn_topology = ops.Topology(batch.edge_index, N, lazy=True)  # queued: no host synchronisation (flags read after the forward)
-        eng.train_step(batch)
+    if args.full:
+        # the reference's shuffled loader hands over a NEW 16-mesh union every step: same step with the
+        # topology rebuilt inside it (mgn_topology_build_async: queued without a host synchronisation)
+        def step_rebuild():
+            batch.mgn_topology = ops.Topology(batch.edge_index, N, lazy=True)  # queued: no host synchronisation (flags read after the forward)
+            eng.train_step(batch)
 
-    k_rb = max(3, args.steps // 3)
-    step_rebuild()
-    dt_rb = timed(step_rebuild, k_rb)
+        k_rb = max(3, args.steps // 3)
+        step_rebuild()
+        dt_rb = timed(step_rebuild, k_rb)
 
-    # rollout (second half of the metric): one mesh batch advanced autoregressively
-    frames = [batch] * args.rollout_steps
-    rollout, rollout_note = (lambda fr: eng.rollout(fr, graph="off")), "eager"
-    # single process only: with a live RCCL process group its watchdog thread polls events, which is
-    # not allowed while another thread captures; at batch 16 replay and eager rollout time the same
-    if args.graph != "off" and world == 1:
-        try:
-            eng.capture_rollout_step(batch)
-            rollout, rollout_note = eng.rollout_graphed, "hipGraph replay"
-        except Exception as ex:  # noqa: BLE001
-            print(f"[bench] hipGraph capture of the rollout step failed ({type(ex).__name__}: {ex}); eager launches", file=sys.stderr)
-    rollout(frames[:3])
-    dt_r = timed(lambda: rollout(frames), 1)
-    rollout_nps = world * N * args.rollout_steps / dt_r
+        # rollout (second half of the metric): one mesh batch advanced autoregressively
+        frames = [batch] * args.rollout_steps
+        rollout, rollout_note = (lambda fr: eng.rollout(fr, graph="off")), "eager"
+        # single process only: with a live RCCL process group its watchdog thread polls events, which is
+        # not allowed while another thread captures; at batch 16 replay and eager rollout time the same
+        if args.graph != "off" and world == 1:
+            try:
+                eng.capture_rollout_step(batch)
+                rollout, rollout_note = eng.rollout_graphed, "hipGraph replay"
+            except Exception as ex:  # noqa: BLE001
+                print(f"[bench] hipGraph capture of the rollout step failed ({type(ex).__name__}: {ex}); eager launches", file=sys.stderr)
+        rollout(frames[:3])
+        dt_r = timed(lambda: rollout(frames), 1)
+        rollout_nps = world * N * args.rollout_steps / dt_r
 
     out = None
     if rank == 0:
@@ -1120,23 +1177,33 @@ def main():
             "config": {"workload": f"BASELINE.json configs[1], {'fp32' if args.precision == 'fp32' else 'bf16'}: {args.batch} x {args.nodes}-node CylinderFlow-like meshes "
                        f"per GPU (N={N}, E={E}), {args.rounds} rounds, latent {args.hidden}, random init", "global_batch_meshes": args.batch * world, "launch": graph_note,
                        "parallelism": f"dp{world}" if world > 1 else "single"},
-            "rollout_node_steps_per_s": round(rollout_nps, 1),
-            "rollout_ms_per_step": round(1e3 * dt_r / args.rollout_steps, 3), "rollout_launch": rollout_note,
-            "topology": {"topology_build_ms": round(topo_ms, 3),
-                         "what": "ops.Topology of the batch (eager build incl. its one host synchronisation): CSR by destination + by source, "
-                                 "outside the headline's timed region (a fixed batch re-uses it); rebuild_every_step queues the build "
-                                 "without a host synchronisation (lazy flags, read once the forward pass is queued)",
-                         "steps_per_s_rebuild_every_step": round(world * k_rb / dt_rb, 3),
-                         "ms_per_step_rebuild_every_step": round(1e3 * dt_rb / k_rb, 3)},
         }
+        if args.full:
+            out.update({
+                "rollout_node_steps_per_s": round(rollout_nps, 1),
+                "rollout_ms_per_step": round(1e3 * dt_r / args.rollout_steps, 3), "rollout_launch": rollout_note,
+                "topology": {"topology_build_ms": round(topo_ms, 3),
+                             "what": "ops.Topology of the batch (eager build incl. its one host synchronisation): CSR by destination + by source, "
+                                     "outside the headline's timed region (a fixed batch re-uses it); rebuild_every_step queues the build "
+                                     "without a host synchronisation (lazy flags, read once the forward pass is queued)",
+                             "steps_per_s_rebuild_every_step": round(world * k_rb / dt_rb, 3),
+                             "ms_per_step_rebuild_every_step": round(1e3 * dt_rb / k_rb, 3)},
+            })
         out["step_floor"] = step_floor(N, E, args.hidden, args.rounds, 1 if args.precision == "bf16" else 6, 1e3 * dt / args.steps)
-        if not args.no_kernel_timing:
+        if args.full and not args.no_kernel_timing:
             device_copy_rate(dev)
             roof, roof_seg, others = kernel_rooflines(gp, ops, capi, eng, batch, dev)
             out["roofline"], out["roofline_scatter"], out["roofline_other_kernels"] = roof, roof_seg, others
-    # free the configs[1] state before the 1M-node record
     if world > 1:
         eng.grad_sync.close()   # the partitioned model below sums its own gradients: stop listening to backward passes
+    if not args.full:   # nothing else to measure: the line is complete
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            torch.distributed.barrier()
+            torch.distributed.destroy_process_group()
+        return
+    # free the configs[1] state before the 1M-node record
     del eng, batch, frames, rollout, step
     torch.cuda.empty_cache()
     if rank == 0 and world == 1 and not args.no_kernel_timing and not args.no_extras:

@@ -27,7 +27,7 @@ def test_two_rank_bench_line():
     env = dict(os.environ, MGN_DIST_BACKEND="gloo", MGN_SHARE_GPU="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--batch", "2", "--nodes", "400", "--rounds", "3", "--rollout-steps", "2", "--no-cpu-baseline",
+           "--batch", "2", "--nodes", "400", "--rounds", "3", "--rollout-steps", "2", "--full", "--no-cpu-baseline",
            "--c4-nodes", "30000", "--c4-steps", "2", "--c5-nodes", "4000"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=REPO)
     assert r.returncode == 0, r.stderr[-3000:]

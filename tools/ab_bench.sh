@@ -6,7 +6,7 @@ cp graph-physics_amd/csrc/libmgn_hip.so /tmp/libmgn_orig.so
 for rep in 1 2; do
   for v in "$@"; do
     cp tools/libexp_$v.so graph-physics_amd/csrc/libmgn_hip.so; touch graph-physics_amd/csrc/libmgn_hip.so
-    echo "== $v: $(python bench.py --no-cpu-baseline --no-kernel-timing 2>&1 | tail -1 | grep -o '"value[^,]*\|rollout_ms[^,]*' | tr '\n' ' ')"
+    echo "== $v: $(python bench.py --full --no-cpu-baseline --no-kernel-timing 2>&1 | tail -1 | grep -o '"value[^,]*\|rollout_ms[^,]*' | tr '\n' ' ')"
   done
 done
 cp /tmp/libmgn_orig.so graph-physics_amd/csrc/libmgn_hip.so

@@ -4,7 +4,7 @@ cd "$(dirname "$0")/.."
 lib=$1; shift
 for rep in $(seq 1 ${REPS:-2}); do
   for v in "$@"; do
-    env $v MGN_LIB=tools/libexp_$lib.so python bench.py --no-cpu-baseline --no-c4 2>/dev/null | tail -1 | python -c "
+    env $v MGN_LIB=tools/libexp_$lib.so python bench.py --full --no-cpu-baseline --no-c4 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 o=d['roofline_other_kernels']

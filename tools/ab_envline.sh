@@ -3,7 +3,7 @@
 cd "$(dirname "$0")/.."
 for rep in $(seq 1 ${REPS:-2}); do
   for v in "$@"; do
-    env $v python bench.py --no-cpu-baseline --no-c4 --steps ${STEPS:-40} --warmup 8 2>/dev/null | tail -1 | python -c "
+    env $v python bench.py --full --no-cpu-baseline --no-c4 --steps ${STEPS:-40} --warmup 8 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 o=d['roofline_other_kernels']

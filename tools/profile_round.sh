@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$R/gpurun_out/prof_${1:-r05}
 rm -rf "$OUT"; mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-timeout 600 rocprofv3 --kernel-trace --stats -d "$OUT/kt" -- python3 "$R/bench.py" --no-cpu-baseline --no-c4 --no-extras --steps 40 --warmup 8 > "$OUT/kt_bench.json" 2> "$OUT/kt.err"
+timeout 600 rocprofv3 --kernel-trace --stats -d "$OUT/kt" -- python3 "$R/bench.py" --full --no-cpu-baseline --no-c4 --no-extras --steps 40 --warmup 8 > "$OUT/kt_bench.json" 2> "$OUT/kt.err"
 timeout 300 rocprofv3 --pmc FETCH_SIZE -d "$OUT/fetch" --output-format csv -- python3 "$R/tools/pmc_step.py" > "$OUT/fetch.log" 2>&1
 timeout 300 rocprofv3 --pmc WRITE_SIZE -d "$OUT/write" --output-format csv -- python3 "$R/tools/pmc_step.py" > "$OUT/write.log" 2>&1
 if [ "${2:-stall}" = "stall" ]; then bash "$R/tools/pmc_stall_passes.sh" "$OUT/stall" > "$OUT/stall.log" 2>&1; fi

@@ -12,7 +12,7 @@ L = capi.lib()
 import bench
 for t in [int(v) for v in sys.argv[1:]] or [0, 100, 200, 300]:
     assert L.mgn_debug_set_stagger(t) == 0
-    sys.argv = ["bench.py", "--no-cpu-baseline", "--no-c4"]
+    sys.argv = ["bench.py", "--full", "--no-cpu-baseline", "--no-c4"]
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
         bench.main()

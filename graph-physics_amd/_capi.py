@@ -60,6 +60,7 @@ class MlpFwdArgs(C.Structure):
         ("seg_key", C.c_void_p), ("seg_rowptr", C.c_void_p), ("seg_out", _f32p), ("seg_part", _f32p),
         ("act", C.c_int),
         ("saveZ", _f32p * MAX_LAYERS),
+        ("add_rows", C.c_int64 * 2),
     ]
 
 
@@ -93,6 +94,7 @@ class MlpBwdArgs(C.Structure):
         ("act", C.c_int),
         ("Zs", _f32p * MAX_LAYERS),
         ("seg_key", C.c_void_p), ("seg_rowptr", C.c_void_p), ("seg_out", _f32p), ("seg_part", _f32p),
+        ("dOut2_rows", C.c_int64),
     ]
 
 

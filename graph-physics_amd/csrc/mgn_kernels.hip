@@ -2262,12 +2262,15 @@ static bool fwd_pp_ok(const mgn_mlp_fwd_args& a) {
 // units back to back, no message output, saves all there or all absent, outputs alias no input) from 65 536 rows (every CU gets
 // >= 8 groups of 32 rows: below that the two-slot lag of its second half is not amortised).  MGN_PPR: unset = on, both modes;
 // 0 = off; 2 = at any size (tests); MGN_PPR_XCD=0: plain hand-out of the groups instead of XCD by XCD (A/B).
+// Its gathers address Pd / Ps rows with 32-bit byte offsets (row * 512): both sources must have a known row count below 2^23.
 static bool fwd_ppr_ok(const mgn_mlp_fwd_args& a) {
   const char* env = getenv("MGN_PPR");
   const int mode = (env == nullptr) ? 1 : atoi(env);
   if (mode == 0) return false;
   const int64_t min_rows = (mode == 2) ? 1 : 65536;
   if (a.precision != 0 || a.y_out != nullptr || a.M < min_rows || a.M * 512 >= (int64_t)1 << 32) return false;  // (32-bit row offsets)
+  for (int q = 0; q < 2; ++q)
+    if (a.add_rows[q] <= 0 || a.add_rows[q] * 512 >= (int64_t)1 << 32) return false;
   for (int u = 1; u < 4; ++u)
     if ((const char*)a.wpk[u] != (const char*)a.wpk[0] + (size_t)u * MGN_WPACK_BYTES) return false;
   const bool all = a.saveU && a.saveR && a.saveH[0] && a.saveH[1] && a.saveH[2] && a.saveM[0] && a.saveM[1] && a.saveM[2];
@@ -2432,7 +2435,7 @@ static bool bwd_x6(const mgn_mlp_bwd_args& a) {
 // The register-resident-weights edge backward chain (mgn_ppr.inc) takes an SbEdge launch when it is fp32-grade, its four units lie
 // back to back, only dscale is asked for as a column sum, every dZ is written as fp32 rows and the outputs alias no input (rows past
 // M are computed as copies of row M - 1 and stored there again), from 65 536 rows.  MGN_PPR as for the forward kernel; MGN_PPR_BWD=0
-// keeps the x6 chain (A/B).
+// keeps the x6 chain (A/B).  Its gather of dOut2 uses 32-bit byte offsets (row * 512): dOut2 needs a known row count below 2^23.
 static bool bwd_ppr_ok(const mgn_mlp_bwd_args& a) {
   const char* env = getenv("MGN_PPR");
   const int mode = (env == nullptr) ? 1 : atoi(env);
@@ -2440,6 +2443,7 @@ static bool bwd_ppr_ok(const mgn_mlp_bwd_args& a) {
   if (mode == 0 || (eb != nullptr && atoi(eb) == 0)) return false;
   const int64_t min_rows = (mode == 2) ? 1 : 65536;
   if (a.precision != 0 || a.M < min_rows || a.M * 512 >= (int64_t)1 << 32 || a.dscale == nullptr) return false;
+  if (a.dOut2_rows <= 0 || a.dOut2_rows * 512 >= (int64_t)1 << 32) return false;
   for (int u = 1; u < 4; ++u)
     if ((const char*)a.wpk[u] != (const char*)a.wpk[0] + (size_t)u * MGN_WPACK_BYTES) return false;
   for (int l = 0; l < 4; ++l)

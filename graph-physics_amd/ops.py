@@ -426,7 +426,7 @@ def mlp_fwd(M: int, H: int, phases: Sequence[Tuple[torch.Tensor, Optional[torch.
     a.saveU, a.saveR = _ptr(saveU), _ptr(saveR)
     a.ldw0, a.n_add, a.n_post, a.post_ldw = ldw0, len(adds), len(posts), post_ldw
     for q, (t, ix) in enumerate(adds):
-        a.add_src[q], a.add_idx[q] = _ptr(t), _ptr(ix)
+        a.add_src[q], a.add_idx[q], a.add_rows[q] = _ptr(t), _ptr(ix), t.shape[0]
     for q, (wptr, o) in enumerate(posts):
         a.post_W[q], a.post_out[q] = wptr, _ptr(o)
     for u, addr in enumerate(wpk):
@@ -462,6 +462,7 @@ def mlp_bwd(M: int, H: int, NL: int, dOut: torch.Tensor, dOut2, idx2, out_w: int
     a = _capi.MlpBwdArgs()
     a.M, a.H, a.NL = M, H, NL
     a.dOut, a.dOut2, a.idx2, a.out_w = _ptr(dOut), _ptr(dOut2), _ptr(idx2), out_w
+    a.dOut2_rows = dOut2.shape[0] if dOut2 is not None else 0
     a.U, a.R, a.scale, a.eps = _ptr(U), _ptr(R), _ptr(scale), EPS
     for l, h in enumerate(Hs or ()):
         a.Hs[l] = _ptr(h)

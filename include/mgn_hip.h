@@ -180,6 +180,10 @@ typedef struct {
    * generic and the split-bf16 kernels (not by the exact-fp32 LDS generation). */
   int act;
   float* saveZ[MGN_MAX_LAYERS];
+  /* add_rows[q]: row count of add_src[q] (the rows add_idx[q] may address).  0 = unknown, which turns the
+   * register-resident-weights edge kernel off: its gathers address rows with 32-bit byte offsets, so it is
+   * taken only when every gathered source has fewer than 2^23 rows of 512 bytes. */
+  int64_t add_rows[2];
 } mgn_mlp_fwd_args;
 #define MGN_ACT_RELU 0
 #define MGN_ACT_SILU 1
@@ -251,6 +255,9 @@ typedef struct {
   const int32_t* seg_rowptr;
   float* seg_out;
   float* seg_part;
+  /* dOut2_rows: row count of dOut2 (the rows idx2 may address).  0 = unknown, which turns the register-resident-
+   * weights edge chain off (32-bit byte offsets in its gathers: taken only below 2^23 rows of 512 bytes). */
+  int64_t dOut2_rows;
 } mgn_mlp_bwd_args;
 size_t mgn_mlp_bwd_workspace_bytes(int64_t M, int H, int NL);
 int mgn_mlp_bwd(const mgn_mlp_bwd_args* args, void* stream);

@@ -6,6 +6,9 @@ exchange falls back to point-to-point copies through the host there; the partiti
 logic and the kernels are the product's).  Forward, loss and every weight gradient must equal the
 un-partitioned oracle, and the gradients must be bit-identical run to run.
 
+The networks here use SiLU or the bf16 matrix mode, which the ShEdge edge kernels (ppr, pp, x6) do not take: the fp32-grade ReLU
+edge kernels on a partitioned mesh are covered by tests/test_hip_halo_edge.py.
+
 The world-4 / world-8 plans are built to hold the shapes an 8-GPU run meets and world 2 cannot:
   * a rank whose nodes are a mesh component of their own: NO boundary nodes, no ghosts, nothing to send --
     it still has to enter every collective (empty splits);

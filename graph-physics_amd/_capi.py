@@ -15,7 +15,7 @@ _CSRC = os.path.join(_HERE, "csrc")
 _REPO = os.path.dirname(_HERE)
 LIB_PATH = os.environ.get("MGN_LIB") or os.path.join(_CSRC, "libmgn_hip.so")
 SOURCES = [os.path.join(_CSRC, "mgn_kernels.hip"), os.path.join(_CSRC, "mgn_prep.hip"), os.path.join(_CSRC, "mgn_attn.hip"),
-           os.path.join(_CSRC, "mgn_dense.hip")]
+           os.path.join(_CSRC, "mgn_dense.hip"), os.path.join(_CSRC, "mgn_loss.hip")]
 DEPS = [os.path.join(_CSRC, "mgn_x6.inc"), os.path.join(_CSRC, "mgn_fused.inc"), os.path.join(_CSRC, "mgn_pp.inc"), os.path.join(_CSRC, "mgn_ppr.inc")]  # included by the source
 HEADER = os.path.join(_REPO, "include", "mgn_hip.h")
 # No packed-fp32 VALU (v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32) in device code: beside a SIMD partner that streams MFMAs
@@ -172,6 +172,25 @@ class TBlock(C.Structure):
     _fields_ = [("src", _f32p), ("dst", _f32p), ("ld_src", C.c_int), ("ld_dst", C.c_int)]
 
 
+MAX_LOSS_TERMS = 8
+
+
+class LossArgs(C.Structure):
+    """mgn_loss_args (include/mgn_hip.h)"""
+    _fields_ = [
+        ("N", C.c_int64), ("O", C.c_int), ("F", C.c_int), ("DX", C.c_int), ("method", C.c_int),
+        ("net_out", _f32p), ("ld_out", C.c_int), ("target", _f32p), ("ld_tgt", C.c_int),
+        ("u_out", _f32p), ("u_tgt", _f32p), ("type", _f32p), ("ldty", C.c_int),
+        ("types", C.c_float * 4), ("ntypes", C.c_int),
+        ("nterms", C.c_int), ("term_type", C.c_int * MAX_LOSS_TERMS), ("term_weight", C.c_float * MAX_LOSS_TERMS),
+        ("rowptr", C.c_void_p), ("col", _i32p), ("coef", _f32p), ("inv", _f32p),
+        ("M", C.c_int64), ("K", C.c_int), ("elems", _i32p), ("cv", _f32p), ("nptr", C.c_void_p), ("nent", _i32p),
+        ("ge_out", _f32p), ("ge_tgt", _f32p),
+        ("g_out", _f32p), ("a_out", _f32p), ("bu_out", _f32p), ("b_out", _f32p), ("part", _f32p),
+        ("terms", _f32p), ("total", _f32p), ("invcount", _f32p),
+    ]
+
+
 #: every symbol include/mgn_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "mgn_version": (C.c_int, []),
@@ -255,6 +274,12 @@ SYMBOLS = {
     "mgn_rownorm_bwd": (C.c_int, [C.c_void_p, C.POINTER(RownormPhase), C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_int64, C.c_void_p,
                                   C.c_void_p, C.c_size_t, C.c_void_p]),
     "mgn_dense_last_error": (C.c_char_p, []),
+    "mgn_loss_fd_geometry": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mgn_loss_ls_geometry": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_int64] + [C.c_void_p] * 6),
+    "mgn_loss_workspace_bytes": (C.c_size_t, []),
+    "mgn_loss_fwd": (C.c_int, [C.POINTER(LossArgs), C.c_void_p]),
+    "mgn_loss_bwd": (C.c_int, [C.POINTER(LossArgs)] + [C.c_void_p] * 5),
+    "mgn_loss_last_error": (C.c_char_p, []),
 }
 
 _lib = None
@@ -367,8 +392,8 @@ def lib():
     return _lib
 
 
-def check(rc: int, what: str, prep: bool = False, attn: bool = False, dense: bool = False):
+def check(rc: int, what: str, prep: bool = False, attn: bool = False, dense: bool = False, loss: bool = False):
     if rc != 0:
-        fn = lib().mgn_dense_last_error if dense else (lib().mgn_attn_last_error if attn else (lib().mgn_prep_last_error if prep else lib().mgn_last_error))
+        fn = lib().mgn_loss_last_error if loss else lib().mgn_dense_last_error if dense else (lib().mgn_attn_last_error if attn else (lib().mgn_prep_last_error if prep else lib().mgn_last_error))
         msg = fn().decode("utf-8", "replace")
         raise RuntimeError(f"{what} failed (code {rc}): {msg}")

@@ -542,9 +542,23 @@ class PartitionedETD(torch.nn.Module):
         return m.decode_module(x_own) if be is None else be.mlp(m.decode_module, x_own)
 
 
-def partitioned_loss(net_out_own, target_own, node_type_own, group=None):
+def check_partitioned_loss(param) -> None:
+    """The partitioned step trains on the masked L2 only: a config whose ``loss`` section asks for anything else is refused here.
+    (The physics losses read the nodal gradient of the physical fields, which on a partition needs the fields' halo rows; the
+    data-parallel step -- whole meshes per rank -- takes every loss.)"""
+    from .parse_parameters import get_loss
+    _, names = get_loss(param or {})
+    if names != "L2LOSS":
+        raise NotImplementedError(f"the partitioned training step supports the L2 loss only; the config's loss section asks for {names} "
+                                  "(train such a config data-parallel, or on one device)")
+
+
+def partitioned_loss(net_out_own, target_own, node_type_own, group=None, param=None):
     """Masked L2 over ALL ranks' NORMAL|OUTFLOW nodes (same value on every rank); its local
-    gradient, SUMMED over ranks (GradAllReduce(average=False)), is the global gradient."""
+    gradient, SUMMED over ranks (GradAllReduce(average=False)), is the global gradient.
+    ``param`` (optional): the training config, checked by ``check_partitioned_loss``."""
+    if param is not None:
+        check_partitioned_loss(param)
     from .nodetype import NodeType
     mask = (node_type_own == int(NodeType.NORMAL)) | (node_type_own == int(NodeType.OUTFLOW))
     w = mask.to(net_out_own.dtype).unsqueeze(1)

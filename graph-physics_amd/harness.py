@@ -21,7 +21,8 @@ import torch
 
 from .mesh import Graph
 from .nodetype import NodeType
-from .parse_parameters import get_model, get_simulator, matrix_precision_from_config
+from .parse_parameters import get_gradient_method, get_loss, get_model, get_simulator, matrix_precision_from_config
+from .losses import L2Loss, LossGeometry, MultiLoss
 from . import ops as _ops
 
 
@@ -190,6 +191,13 @@ class Engine:
         _ops.set_matrix_precision(matrix_precision_from_config(param))  # bf16-mixed <=> enable_vram_optimizations
         self.model = get_model(param)
         self.sim = get_simulator(param, self.model, device)
+        # the config's "loss" section (lightning_module.py:86-96); without one: the masked L2, on the code path it always took
+        self.loss, self.loss_name = get_loss(param)
+        self.gradient_method = get_gradient_method(param)
+        self.loss_masks = (NodeType.NORMAL, NodeType.OUTFLOW)
+        #: per-term device scalars of the last step of a MultiLoss config, in the order of ``loss_name`` (what the reference logs as
+        #: ``train_<name>``: the WEIGHTED terms); None for a single loss
+        self.last_losses = None
         self.learning_rate, self.num_steps, self.warmup, self.grad_clip = learning_rate, num_steps, warmup, grad_clip
         self.opt = self._make_optimizer(learning_rate, capturable=False)
         self.step_count = 0
@@ -215,6 +223,31 @@ class Engine:
                 pass
         return torch.optim.AdamW(params, capturable=capturable, **kw) if capturable else torch.optim.AdamW(params, **kw)
 
+    def _loss(self, batch: Graph, net_out: torch.Tensor, target: torch.Tensor, node_type: torch.Tensor) -> torch.Tensor:
+        """the training step's loss (lightning_module.py:278-312)"""
+        if isinstance(self.loss, L2Loss):
+            return l2_loss(net_out, target, node_type)
+        if not isinstance(self.loss, MultiLoss):
+            return self.loss(graph=batch, target=target, network_output=net_out, node_type=node_type, masks=self.loss_masks,
+                             gradient_method=self.gradient_method)
+        u_out = u_tgt = geom = None
+        if self.loss.needs_physical_fields:
+            # the geometry of this batch object: pinned on it by the first step that sees it (never built inside a capture)
+            geom = LossGeometry.for_graph(batch, self.gradient_method)
+            # Simulator.build_outputs of the output and of the normalised target (lightning_module.py:279-280), after this step's
+            # normaliser accumulation; the statistics are formed once for both
+            nz = self.sim._output_normalizer
+            with torch.no_grad():
+                std, mean = nz._std_with_epsilon(), nz._mean()
+                pre = self.sim._get_pre_target(batch)
+                u_tgt = pre + (target * std + mean)
+            u_out = pre + (net_out * std + mean)
+        total, terms = self.loss(graph=batch, target=target, network_output=net_out, node_type=node_type, masks=self.loss_masks,
+                                 network_output_physical=u_out, target_physical=u_tgt, gradient_method=self.gradient_method,
+                                 return_all_losses=True, geometry=geom)
+        self.last_losses = [t.detach() for t in terms]
+        return total
+
     def train_step(self, batch: Graph) -> torch.Tensor:
         self.sim.train()
         lr_now = self.learning_rate * lr_factor(self.step_count, self.warmup, self.num_steps)
@@ -226,7 +259,7 @@ class Engine:
                 g["lr"] = lr_now
         node_type = batch.x[:, self.sim.node_type_index]
         net_out, target, _ = self.sim(batch)
-        loss = l2_loss(net_out, target, node_type)
+        loss = self._loss(batch, net_out, target, node_type)
         self.opt.zero_grad(set_to_none=True)
         loss.backward()
         if self.grad_sync is not None:
@@ -250,6 +283,9 @@ class Engine:
         ~1 us per node.  The mesh topology and tensor shapes are frozen in the graph: capture
         once per mesh/batch shape, feed new data through ``train_step_graphed`` (copied into the
         static input tensors).  The learning rate lives in a device tensor updated before replay.
+        With a physics loss the mesh GEOMETRY (``losses.LossGeometry``) is frozen too: it is built by the
+        eager warm-up steps and pinned on the static batch; ``last_losses`` then holds the captured step's
+        per-term scalars, refreshed by every replay.
         """
         dev = self.device
         assert self.grad_sync is None, "graph capture of the multi-GPU step is not supported yet"
@@ -276,7 +312,7 @@ class Engine:
         def body():
             node_type = self._static.x[:, self.sim.node_type_index]
             net_out, target, _ = self.sim(self._static)
-            loss = l2_loss(net_out, target, node_type)
+            loss = self._loss(self._static, net_out, target, node_type)
             self.opt.zero_grad(set_to_none=True)
             loss.backward()
             if isinstance(self.opt, FusedClipAdamW):
@@ -307,7 +343,8 @@ class Engine:
         if batch is not None and batch is not self._static:
             self._static.x.copy_(batch.x, non_blocking=True)
             self._static.y.copy_(batch.y, non_blocking=True)
-            self._static.edge_attr.copy_(batch.edge_attr, non_blocking=True)
+            if self._static.edge_attr is not None:   # (a Transformer config has no edge features)
+                self._static.edge_attr.copy_(batch.edge_attr, non_blocking=True)
         self._lr_t.fill_(self.learning_rate * lr_factor(self.step_count, self.warmup, self.num_steps))
         self._graph.replay()
         self.step_count += 1

@@ -2,11 +2,12 @@
 reference factories (graphphysics/training/parse_parameters.py:81-190)."""
 from __future__ import annotations
 
-from typing import Any, Dict
+from typing import Any, Dict, List, Optional, Tuple, Union
 
 import torch
 
 from .layers import set_use_silu_activation
+from .losses import LossType, MultiLoss, PHYSICS_LOSSES, check_gradient_method
 from .nodetype import NodeType
 from .processors import EncodeProcessDecode
 from .simulator import Simulator
@@ -66,6 +67,52 @@ def get_simulator(param: Dict[str, Any], model, device: torch.device) -> Simulat
         model=model,
         device=device,
     )
+
+
+def _loss_type(name: str) -> LossType:
+    try:
+        return LossType[str(name).upper()]
+    except KeyError:
+        raise ValueError(f"loss.type: unknown loss '{name}' (one of {', '.join(t.name.lower() for t in LossType)})") from None
+
+
+def get_gradient_method(param: Dict[str, Any], **kwargs) -> Optional[str]:
+    """``loss.gradient_method`` ("finite_diff" / "least_squares"), or None when the config names none
+    (training/parse_parameters.py:326-340)"""
+    try:
+        method = param["loss"]["gradient_method"]
+    except KeyError:
+        return None
+    return None if method is None else check_gradient_method(method)
+
+
+def get_loss(param: Dict[str, Any], **kwargs) -> Tuple[Any, Union[str, List[str]]]:
+    """The loss object of the config's ``loss`` section and its name(s) (training/parse_parameters.py:300-323): no section ->
+    ``L2Loss``, one type -> that loss and its ``LossType`` name, several -> ``MultiLoss`` and the list of names.
+
+    Configurations the reference accepts here and then fails on inside the first training step (a ``NameError`` /
+    ``TypeError``) are refused now, with a ``ValueError`` that names the key."""
+    if "loss" not in param:
+        return LossType.L2LOSS.value(**kwargs), LossType.L2LOSS.name
+    section = param["loss"]
+    types = section.get("type")
+    if isinstance(types, str) or not types:
+        raise ValueError("loss.type: a non-empty list of loss names")
+    kinds = [_loss_type(t) for t in types]
+    method = get_gradient_method(param)   # validates the name
+    if len(kinds) > 1:
+        weights = section.get("weights")
+        if weights is None or len(weights) != len(kinds):
+            raise ValueError(f"loss.weights: {0 if weights is None else len(weights)} weights for {len(kinds)} loss types")
+        if method is None:
+            raise ValueError("loss.gradient_method: several loss types need a gradient method ('finite_diff' or 'least_squares')")
+        return MultiLoss([k.value(**kwargs) for k in kinds], list(weights)), [k.name for k in kinds]
+    if "weights" in section and section["weights"] is not None and len(section["weights"]) != 1:
+        raise ValueError(f"loss.weights: {len(section['weights'])} weights for 1 loss type")
+    if kinds[0] in PHYSICS_LOSSES:
+        raise ValueError(f"loss.type: '{types[0]}' alone is not trainable: the single-loss training step passes no physical fields; "
+                         "list it with at least one more loss type")
+    return kinds[0].value(**kwargs), kinds[0].name
 
 
 def matrix_precision_from_config(param: Dict[str, Any]) -> str:

@@ -688,6 +688,65 @@ int mgn_rownorm2_bwd(const float* dn, const float* x, int ldx, int K, const floa
                      float* dscale_io, void* ws, size_t ws_bytes, void* stream);
 const char* mgn_dense_last_error(void);
 
+/* ================================================================================
+ * A training config's "loss" section (graphphysics/utils/loss.py, utils/vectorial_operators.py) -- csrc/mgn_loss.hip
+ * ================================================================================
+ * total = sum_t weight_t * loss_t over up to 8 terms, every loss_t the mean over the rows whose node type is one of `types` (and over
+ * that row's elements).  Pointwise terms read the normalised net_out / target [N, O]; physics terms read the physical fields
+ * u_out / u_tgt [N, F] (dense) and their nodal spatial gradient G [N, F, DX], which the node pass forms in registers:
+ *   finite_diff    G[n] = inv[n] * sum_{m in row n} (U[m] - U[n]) (x) coef[n->m]      over the de-duplicated symmetric neighbour CSR
+ *   least_squares  G[n] = inv[n] * sum_{(e, k) of n} ge[e],  ge[e] = sum_k U[elems[e, k]] (x) cv[e, k]   (the one [M, F, DX] intermediate)
+ * Geometry (coef / cv / inv) is computed once per mesh in fp64 and stored as fp32 (mgn_loss_*_geometry); a mesh whose positions
+ * change needs a new one.  No atomics: results are bit-identical run to run.  No host synchronisation: capturable.
+ * F <= 4, DX <= 3, O >= 1.  Returns 0, 1 (bad arguments), 2 (HIP error): mgn_loss_last_error(). */
+#define MGN_LOSS_MAX_TERMS 8
+#define MGN_LOSS_MAX_F 4
+#define MGN_LOSS_MAX_D 3
+#define MGN_LOSS_L2 0              /* (out - target)^2                                   per element of [N, O] */
+#define MGN_LOSS_COSINE 1          /* 1 - <out, target> / sqrt((|out|^2 + 1e-12)(|target|^2 + 1e-12))   per row */
+#define MGN_LOSS_L1SMOOTH 2        /* smooth_l1(out - target, beta = 1)                  per element of [N, O] */
+#define MGN_LOSS_GRADIENT 3        /* (G_out - G_tgt)^2                                  per element of [N, F, DX] */
+#define MGN_LOSS_CONVECTION 4      /* (c_out - c_tgt)^2, c[n, f] = U[n, f] * sum_d G[n, f, d]      per element of [N, F] */
+#define MGN_LOSS_DIV_L2 5          /* div^2, div[n] = sum_{k < min(F, DX)} G_out[n, k, k]          per row */
+#define MGN_LOSS_DIV_L1 6          /* |div| */
+#define MGN_LOSS_DIV_L1SMOOTH 7    /* smooth_l1(div, beta = 1) */
+#define MGN_LOSS_FINITE_DIFF 0
+#define MGN_LOSS_LEAST_SQUARES 1
+typedef struct {
+  int64_t N; int O; int F; int DX; int method;
+  const float* net_out; int ld_out;          /* [N, O] rows, pitch in elements */
+  const float* target; int ld_tgt;
+  const float* u_out; const float* u_tgt;    /* [N, F] dense; NULL: no physics term */
+  const float* type; int ldty;               /* node type of row n at type[n * ldty] */
+  float types[4]; int ntypes;
+  int nterms; int term_type[MGN_LOSS_MAX_TERMS]; float term_weight[MGN_LOSS_MAX_TERMS];
+  /* finite_diff geometry */
+  const int64_t* rowptr; const int32_t* col; const float* coef;   /* [N + 1], [nnz], [nnz, DX] */
+  const float* inv;                          /* [N]: 1 / (weight sum + 1e-8), or 1 / clamp(measure sum, 1e-12) for least_squares */
+  /* least_squares geometry */
+  int64_t M; int K;                          /* M elements of K corners (3 or 4) */
+  const int32_t* elems; const float* cv;     /* [M, K], [M, K, DX] */
+  const int64_t* nptr; const int32_t* nent;  /* node -> entries e * K + k of elems, [N + 1], [M * K] */
+  float* ge_out; float* ge_tgt;              /* [M, F, DX] scratch (written by the forward) */
+  /* outputs */
+  float* g_out;                              /* optional [N, F, DX]: G of u_out */
+  float* a_out; float* bu_out; float* b_out; /* [N, F, DX], [N, F], [N, O]: per-node derivatives kept for the backward */
+  float* part;                               /* mgn_loss_workspace_bytes() of scratch */
+  float* terms; float* total; float* invcount;   /* [nterms] weighted terms, their sum, 1 / selected rows (device scalars) */
+} mgn_loss_args;
+/* neighbour CSR rows without self entries; self_loop (optional, [N]) != 0 where the edge list holds a pair (n, n) */
+int mgn_loss_fd_geometry(const int64_t* rowptr, const int32_t* col, const uint8_t* self_loop, const float* pos, int DX, int64_t N,
+                         float* coef, float* inv, void* stream);
+/* triangles in 2-D / 3-D (K = 3) or tetrahedra in 3-D (K = 4); vol: [M] doubles of scratch */
+int mgn_loss_ls_geometry(const int32_t* elems, int64_t M, int K, const float* pos, int DX, int64_t N, const int64_t* nptr,
+                         const int32_t* nent, float* cv, double* vol, float* inv, void* stream);
+size_t mgn_loss_workspace_bytes(void);
+int mgn_loss_fwd(const mgn_loss_args* args, void* stream);
+/* from the buffers the forward left in args: d_net [N, O] (optional) = d total / d net_out, d_u [N, F] (optional) = d total / d u_out;
+ * g: the incoming gradient of total (device scalar); dge: [M, F, DX] scratch for least_squares */
+int mgn_loss_bwd(const mgn_loss_args* args, const float* g, float* d_net, float* d_u, float* dge, void* stream);
+const char* mgn_loss_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif

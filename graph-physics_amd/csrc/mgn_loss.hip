@@ -64,7 +64,11 @@ __global__ void __launch_bounds__(256) k_fd_geom(const int64_t* __restrict__ row
 // corner values with C = pinv(A) (DX x S): corner s + 1 carries column s, corner 0 minus their sum.  Stored: cv[e, k, :] = C column * vol_e.
 // S == DX: adjugate / determinant.  S = 2 in 3-D: Gram-Schmidt of the two edge vectors, then the 2 x 2 triangular solve in that
 // basis (the minimum-norm solution).  Never the Gram matrix A A^T: it squares the condition number, and hull slivers reach 2.5e4.
-// An element of zero measure contributes nothing.
+// An element of zero measure contributes nothing -- and zero means zero to fp64 rounding: collinear corners off the axes, or a
+// corner listed twice, leave a determinant (or a Gram-Schmidt remainder) of 1e-17 rather than 0, and C * vol of such an element is
+// not small (C ~ 1 / det): it would be adj(A) / 6, as large as a sound element's coefficients.  So a measure under LS_FLAT of the
+// product of the edge lengths counts as zero; distinct fp32 positions cannot make a sine that small except by being collinear.
+#define LS_FLAT 1.5e-14   // ~ 64 fp64 epsilons
 __global__ void __launch_bounds__(256) k_ls_elem_geom(const int32_t* __restrict__ elems, long M, int K, const float* __restrict__ pos, int DX,
                                                       float* __restrict__ cv, double* __restrict__ vol) {
   const long e = (long)blockIdx.x * 256 + threadIdx.x;
@@ -80,8 +84,9 @@ __global__ void __launch_bounds__(256) k_ls_elem_geom(const int32_t* __restrict_
   double v = 0.0;
   if (S == 2 && DX == 2) {
     const double det = A[0][0] * A[1][1] - A[0][1] * A[1][0];
-    v = 0.5 * fabs(det);
-    if (det != 0.0) {   // A^-1 = adj / det; C[d][s] = (A^-1)[d][s]
+    const double len = sqrt((A[0][0] * A[0][0] + A[0][1] * A[0][1]) * (A[1][0] * A[1][0] + A[1][1] * A[1][1]));
+    if (fabs(det) > LS_FLAT * len) {   // A^-1 = adj / det; C[d][s] = (A^-1)[d][s]
+      v = 0.5 * fabs(det);
       C[0][0] = A[1][1] / det, C[0][1] = -A[0][1] / det;
       C[1][0] = -A[1][0] / det, C[1][1] = A[0][0] / det;
     }
@@ -89,8 +94,10 @@ __global__ void __launch_bounds__(256) k_ls_elem_geom(const int32_t* __restrict_
     const double c00 = A[1][1] * A[2][2] - A[1][2] * A[2][1], c01 = A[1][2] * A[2][0] - A[1][0] * A[2][2],
                  c02 = A[1][0] * A[2][1] - A[1][1] * A[2][0];
     const double det = A[0][0] * c00 + A[0][1] * c01 + A[0][2] * c02;
-    v = fabs(det) / 6.0;
-    if (det != 0.0) {   // (A^-1)[d][s] = cofactor[s][d] / det
+    double len = 1.0;
+    for (int s = 0; s < 3; ++s) len *= sqrt(A[s][0] * A[s][0] + A[s][1] * A[s][1] + A[s][2] * A[s][2]);
+    if (fabs(det) > LS_FLAT * len) {   // (A^-1)[d][s] = cofactor[s][d] / det
+      v = fabs(det) / 6.0;
       C[0][0] = c00 / det, C[1][0] = c01 / det, C[2][0] = c02 / det;
       C[0][1] = (A[0][2] * A[2][1] - A[0][1] * A[2][2]) / det;
       C[1][1] = (A[0][0] * A[2][2] - A[0][2] * A[2][0]) / det;
@@ -107,8 +114,9 @@ __global__ void __launch_bounds__(256) k_ls_elem_geom(const int32_t* __restrict_
       const double r01 = q0[0] * A[1][0] + q0[1] * A[1][1] + q0[2] * A[1][2];
       for (int d = 0; d < 3; ++d) w[d] = A[1][d] - r01 * q0[d];
       const double r11 = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
-      v = 0.5 * r00 * r11;
-      if (r11 > 0.0) {
+      const double len1 = sqrt(A[1][0] * A[1][0] + A[1][1] * A[1][1] + A[1][2] * A[1][2]);
+      if (r11 > LS_FLAT * len1) {   // r11 / |a1| is the sine of the corner angle
+        v = 0.5 * r00 * r11;
         for (int d = 0; d < 3; ++d) {
           q1[d] = w[d] / r11;
           C[d][0] = q0[d] / r00 - q1[d] * r01 / (r00 * r11);

@@ -145,14 +145,10 @@ __device__ __forceinline__ float head_reduce_own(const float (&p)[4], int l) {
 // [r5] XCD-aware block order: consecutive workgroups go to consecutive XCDs, each with an L2 of its own, so with rows handed out in
 // blockIdx order every L2 saw rows from everywhere.  Block b serves row block (b & 7) * (gridDim / 8) + (b >> 3) instead: an XCD
 // walks ONE contiguous eighth of the (Morton-ordered) rows, and the k / v (q / dy) rows its workgroups gather are mostly rows its own
-// L2 already holds.  -DATTN_NO_XCD_ORDER: blockIdx order.
+// L2 already holds.
 __device__ __forceinline__ long attn_block() {
-#ifdef ATTN_NO_XCD_ORDER
-  return (long)blockIdx.x;
-#else
   const unsigned per = gridDim.x >> 3, b = blockIdx.x;
   return (b < 8 * per) ? (long)(b & 7) * per + (b >> 3) : (long)b;
-#endif
 }
 
 // The edge loops below are software-pipelined by hand: the column index of edge e + 2 and the gathered rows of edge e + 1 are
@@ -174,9 +170,6 @@ __device__ __forceinline__ float bf16r(float x) {
 // (v_exp_f32 on t itself, corrected to first order in r: 6 instructions) was measured 4x noisier on the cancelling key-bias
 // gradient and is not used.  These kernels are bound by vector-instruction issue, not by bytes ([r4]).
 __device__ __forceinline__ float exp_sm(float x) {
-#ifdef ATTN_EXPF
-  return expf(x);
-#endif
   constexpr float L2E_HI = 1.44269502162933349609375f, L2E_LO = 1.925963033500011e-8f;
   // [r5] exp(-150) is an exact 0 after the ldexp; clamping keeps n inside int range and r bounded whatever the score magnitude
   // (the -1e37 start of the running maximum, or |score| >= 3e29, used to reach fptosi's undefined range); a NaN stays a NaN

@@ -217,10 +217,8 @@ __global__ void __launch_bounds__(256) k_linear(const mgn_linear_args a, const i
       const size_t nxt = (size_t)16 * ((ob + 1 < NB) ? ob + 1 : ob) * a.ldw;   // (the last block re-requests its own: an unconditional load)
 #pragma unroll
       for (int kb = 0; kb < KB; ++kb) {
-#ifndef LIN_EXP_NOW
         wa[kb] = *(const f32x4*)(w1 + nxt + 16 * kb);
         if (GATE) wb[kb] = *(const f32x4*)(w2 + nxt + 16 * kb);
-#endif
       }
     } else if (LDSW) {
 #pragma unroll
@@ -254,11 +252,7 @@ __global__ void __launch_bounds__(256) k_linear(const mgn_linear_args a, const i
     for (int kb = 0; kb < KB; ++kb) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-#ifdef LIN_EXP_NOMFMA   // timing experiment only
-        acc[r] += ca[kb][r] * in[kb][r];
-#else
         acc = MFMA16(ca[kb][r], in[kb][r], acc);
-#endif
         if (GATE) acc2 = MFMA16(cb[kb][r], in[kb][r], acc2);
       }
     }
@@ -270,22 +264,14 @@ __global__ void __launch_bounds__(256) k_linear(const mgn_linear_args a, const i
     }
     f32x4 y;
 #pragma unroll
-#ifdef LIN_EXP_NOACT   // timing experiment only: what the activation (erf / exp per element) costs
-    for (int r = 0; r < 4; ++r) y[r] = acc[r];
-#else
     for (int r = 0; r < 4; ++r) y[r] = d_act(acc[r], a.act);
-#endif
     if (BF && a.act >= 0) y = bf16r4(y);
     if (GATE) {
       y = y * acc2;
       if (BF) y = bf16r4(y);
     }
     if (a.resid != nullptr) y = *(const f32x4*)(a.resid + mm * a.ldr + n0) + y;   // the residual stream stays fp32
-#ifdef LIN_EXP_NOSTORE
-    if (valid && y[0] == 12345.678f) *(f32x4*)(a.out + mm * a.ldo + n0) = y;
-#else
     if (valid) *(f32x4*)(a.out + mm * a.ldo + n0) = y;
-#endif
   }
   }  // tiles
 }

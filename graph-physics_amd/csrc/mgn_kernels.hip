@@ -30,30 +30,16 @@ typedef __attribute__((address_space(1))) const f32x4 g_cf32x4;
 typedef __attribute__((address_space(1))) f32x4 g_f32x4;
 typedef __attribute__((address_space(1))) const float g_cfloat;
 typedef __attribute__((address_space(1))) float g_float;
-#ifdef MGN_EXP_NOLOAD   // timing experiment only: rows are not fetched
-__device__ __forceinline__ f32x4 ld4(const float* p) { return f32x4{1.f, 2.f, (float)(size_t)p, 0.5f}; }
-#else
 __device__ __forceinline__ f32x4 ld4(const float* p) { return *(g_cf32x4*)p; }
-#endif
-#ifdef MGN_EXP_NOSTORE  // timing experiment only: results are dropped unless they are NaN (keeps the math alive)
-__device__ __forceinline__ void st4(float* p, f32x4 v) { if (v[0] != v[0]) *(g_f32x4*)p = v; }
-#else
 __device__ __forceinline__ void st4(float* p, f32x4 v) { *(g_f32x4*)p = v; }
-#endif
 // Write-once data that is only read again much later (saved activations for the backward pass).  A store
 // instruction covers 64 B of each of 16 rows -- HALF a 128-byte line -- and the other half follows one
 // instruction later: through plain stores the XCD's L2 merges the halves into whole-line write-backs;
 // non-temporal stores (the round-1 choice, -2.7 % on the exact-fp32 generation) let them leave separately
 // and cost the packed kernel 12 % more write traffic (545 vs 487 MB per launch, WRITE_SIZE) and 6 % of its
-// time (239/232/237 vs 224/222/221 us, alternating A/B in one GPU call).  -DMGN_EXP_NT_SAVES rebuilds the
-// non-temporal variant.
-#ifdef MGN_EXP_NOSTORE
-__device__ __forceinline__ void st4_stream(float* p, f32x4 v) { if (v[0] != v[0]) *(g_f32x4*)p = v; }
-#elif defined(MGN_EXP_NT_SAVES)
-__device__ __forceinline__ void st4_stream(float* p, f32x4 v) { __builtin_nontemporal_store(v, (g_f32x4*)p); }
-#else
+// time (239/232/237 vs 224/222/221 us, alternating A/B in one GPU call).  So these stay plain stores; the name marks
+// the call sites.
 __device__ __forceinline__ void st4_stream(float* p, f32x4 v) { *(g_f32x4*)p = v; }
-#endif
 __device__ __forceinline__ float ld1(const float* p) { return *(g_cfloat*)p; }
 __device__ __forceinline__ void st1(float* p, float v) { *(g_float*)p = v; }
 
@@ -719,23 +705,6 @@ extern "C" int mgn_debug_timeline(unsigned long long* out, int* pos) {
 #define TL_STAMP(tag) ((void)0)
 #define TL_DUMP() ((void)0)
 #endif
-// Stagger the second dispatch round (blocks >= 256 share CUs with blocks < 256) so that the two
-// co-resident workgroups are half a GEMM period out of phase instead of in lock-step.
-__device__ __forceinline__ void stagger_start(int cycles) {
-#ifdef MGN_EXP_STAGGER
-  if (blockIdx.x >= 256) {
-    const unsigned long long t0 = __builtin_readcyclecounter();
-    while (__builtin_readcyclecounter() - t0 < (unsigned long long)cycles) __builtin_amdgcn_s_sleep(8);
-  }
-#else
-  (void)cycles;
-#endif
-}
-#ifdef MGN_EXP_NOSYNC
-#define MGN_SYNC() ((void)0)
-#else
-#define MGN_SYNC() __syncthreads()
-#endif
 // arr[i] for a small kernel-argument pointer array WITHOUT a dynamic (SMEM) load: every
 // element is read with a constant index (hoisted to SGPRs once) and picked by a select
 // chain.  A scalar load inside the GEMM loop is poison: SMEM returns out of order, so while
@@ -827,11 +796,6 @@ __device__ __forceinline__ DmaJob dma_prepare(const float* __restrict__ Wk, int 
 __device__ __forceinline__ void dma_issue(const DmaJob& j, int i) {
   if (j.on) glds16(j.su0 + (size_t)i * j.stride, j.vo[i & 3], j.lds0 + i * 1024);
 }
-__device__ __forceinline__ void dma_weights(const float* __restrict__ Wk, int ldw, int hk, lds_char* buf, int wv, int lane) {
-  const DmaJob j = dma_prepare(Wk, ldw, hk, buf, wv, lane, true);
-#pragma unroll
-  for (int i = 0; i < 8; ++i) dma_issue(j, i);
-}
 
 // acc += W[:, 64*HK .. 64*HK+63](LDS) * in[4*HK .. 4*HK+3]; the consumed input blocks are
 // refilled from nxt (prefetch of the next tensor, see gemm_full); `job` = the DMA of the half
@@ -890,7 +854,6 @@ __global__ void __launch_bounds__(256, 2) k_mlp_fwd_lds(const mgn_mlp_fwd_args a
   const long ntiles = (a.M + 64 * MT - 1) / (64 * MT);
   long tile = blockIdx.x;
   if (tile >= ntiles) return;
-  stagger_start(6000);
   const long my_tiles = (ntiles - tile + gridDim.x - 1) / gridDim.x;
   int off[4];
 #pragma unroll
@@ -1552,12 +1515,10 @@ __global__ void __launch_bounds__(256, 2) k_wgrad_lds(const WgradLaunch L) {
 #pragma unroll
       for (int quad = 0; quad < WG_TILE_ROWS / 4; ++quad) {
         if (quad + 1 < WG_TILE_ROWS / 4) ld_quad(ta, tb, quad + 1, av[(quad + 1) & 1], bv[(quad + 1) & 1]);
-#ifndef MGN_EXP_NODMA
         if (more && quad < 4) {  // next tile's DMA: two pieces per quad, early, under the MFMAs
           dma_row_piece(J.A, (tile + 1) * WG_TILE_ROWS, J.M, nb0, wv, lane, quad);
           dma_row_piece(J.B, (tile + 1) * WG_TILE_ROWS, J.M, nb0 + WG_TILE_BYTES, wv, lane, quad);
         }
-#endif
         __builtin_amdgcn_sched_barrier(0);
         if (decltype(TAIL)::value) {
           const float keep = (4 * quad + g < rows_left) ? 1.f : 0.f;
@@ -2155,11 +2116,6 @@ static int check_launch(const char* what) {
   }
   return 0;
 }
-static int pick_mt(int64_t M) {
-  // enough 16*MT-row wave tiles to give each of the 1024 SIMDs ~2 waves
-  if (M >= (int64_t)64 * 2048) return 2;
-  return 1;
-}
 
 struct MlpPlan {
   bool lds;       // LDS-weight kernel (H = 128, full widths)
@@ -2193,13 +2149,12 @@ static MlpPlan plan_mlp(int64_t M, int H, int NL, bool ragged, bool bwd, int act
 }
 
 template <typename K>
-static int set_smem(K kern, size_t bytes) {
+static int set_smem(K kern) {
   static thread_local const void* done[16];
   static thread_local int ndone = 0;
   for (int i = 0; i < ndone; ++i)
     if (done[i] == (const void*)kern) return 0;
   if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * WBUF_BYTES + 4 * 7 * 128 * 4)) != hipSuccess) return 1;
-  (void)bytes;
   if (ndone < 16) done[ndone++] = (const void*)kern;
   return 0;
 }
@@ -2284,8 +2239,8 @@ static int launch_fwd(const mgn_mlp_fwd_args& a, hipStream_t s) {
   const bool ragged = fwd_ragged(a);
   const MlpPlan p = plan_mlp(a.M, a.H, a.NL, ragged, false, a.act);
   if (p.lds && fwd_x6(a)) {
-    // 8-wave workgroups (one per CU) when every CU still gets a tile; MGN_NW=4/8 overrides
-    int nw = (a.M >= 128 * 256) ? X6_FWD_NW_LARGE : 4;
+    // 4 waves per workgroup at every M (8-wave workgroups, one per CU, are the MGN_NW=8 override)
+    int nw = 4;
     bool nw6 = false;  // MGN_NW=6: the three-waves-per-SIMD instance of the edge update (experiment)
     if (const char* e = getenv("MGN_NW")) {
       nw = (atoi(e) == 8) ? 8 : 4;
@@ -2389,10 +2344,10 @@ static int launch_fwd(const mgn_mlp_fwd_args& a, hipStream_t s) {
   }
   if (p.lds) {
     if (p.mt == 2) {
-      if (set_smem(k_mlp_fwd_lds<2>, p.smem)) return 1;
+      if (set_smem(k_mlp_fwd_lds<2>)) return 1;
       hipLaunchKernelGGL((k_mlp_fwd_lds<2>), dim3(p.grid), dim3(256), p.smem, s, a);
     } else {
-      if (set_smem(k_mlp_fwd_lds<1>, p.smem)) return 1;
+      if (set_smem(k_mlp_fwd_lds<1>)) return 1;
       hipLaunchKernelGGL((k_mlp_fwd_lds<1>), dim3(p.grid), dim3(256), p.smem, s, a);
     }
     return 0;
@@ -2529,10 +2484,10 @@ static int launch_bwd(const mgn_mlp_bwd_args& a, hipStream_t s) {
   }
   if (p.lds) {
     if (p.mt == 2) {
-      if (set_smem(k_mlp_bwd_lds<2>, p.smem)) return 1;
+      if (set_smem(k_mlp_bwd_lds<2>)) return 1;
       hipLaunchKernelGGL((k_mlp_bwd_lds<2>), dim3(p.grid), dim3(256), p.smem, s, a);
     } else {
-      if (set_smem(k_mlp_bwd_lds<1>, p.smem)) return 1;
+      if (set_smem(k_mlp_bwd_lds<1>)) return 1;
       hipLaunchKernelGGL((k_mlp_bwd_lds<1>), dim3(p.grid), dim3(256), p.smem, s, a);
     }
     return 0;

@@ -33,10 +33,6 @@
 // Static shape = ShEdge of mgn_x6.inc (4 layers, ReLU, RMSNorm, residual, two gathered adds, fused segment sum), fp32-grade
 // (6 terms).  Same arithmetic in the same order as k_mlp_fwd_x6<6, 4, 0, ShEdge>: outputs are bit-identical to it.
 
-#ifndef PP_PRIO_C
-#define PP_PRIO_C 2  /* wave priority inside a GEMM quarter / inside a free slot (experiment knobs) */
-#define PP_PRIO_F 0
-#endif
 #define PP_STAGE_BYTES 8192
 #define PP_CST_BYTES (5 * 512)
 #define PP_LDS_BYTES (X6_RING * X6_QBYTES + PP_CST_BYTES + 8 * PP_STAGE_BYTES)
@@ -387,18 +383,14 @@ __global__ void __launch_bounds__(512, 2) k_edge_fwd_pp(const mgn_mlp_fwd_args a
     PP_STAMP(0);
     pp_barrier();
     PP_STAMP(1);
-    __builtin_amdgcn_s_setprio(PP_PRIO_C);
-#ifndef PP_EXP_NOC  // timing experiment only (results are garbage): the stream without its GEMM quarters
+    __builtin_amdgcn_s_setprio(2);  // wave priority: 2 inside a GEMM quarter, 0 inside a free slot
     pp_gemm_q(acc, xs, ring + cslot * X6_QBYTES + lane16, wf);
-#endif
-    __builtin_amdgcn_s_setprio(PP_PRIO_F);
+    __builtin_amdgcn_s_setprio(0);
     PP_STAMP(2);
     pp_barrier();
     PP_STAMP(3);
     int nv = 0;
-#ifndef PP_EXP_NOF  // timing experiment only (results are garbage): the stream without its free-slot work
     work(nv);
-#endif
     close_slot(nv);
   };
 

@@ -42,31 +42,7 @@
 // the two 64-byte halves of a 128-byte line in consecutive instructions, so nothing is lost by not merging them in L2 (the x6 kernels
 // paid +12 % write traffic for it), and the write-back cache no longer sits between a store and its acknowledgement: the counted
 // waits for the LDS-DMA rows stop queueing behind the stores of the boundary before (186 -> 149-161 us for the training-mode forward,
-// alternating in one GPU call).  e' / dE (re-read by the next launch) stay plain.
-#ifndef PPR_NT_SAVES
-#define PPR_NT_SAVES 1
-#endif
-#ifndef PPB_NT_DZ
-#define PPB_NT_DZ 1
-#endif
-#ifndef PPB_NT_DE
-#define PPB_NT_DE 1
-#endif
-// 1: the gathered rows Pd[dst] / Ps[src] of a group are asked for by the SECOND half's waves, in their first boundary phase -- one phase
-// earlier than the first half could (the buffer is free as soon as the first half's unit-0 boundary has read it), and waited for at the
-// end of their epilogue phase: 2.5 phases to land instead of 1.5, and the first half's heaviest boundary loses four LDS-DMA pairs
-#ifndef PPR_GATHER_H1
-#define PPR_GATHER_H1 1
-#endif
-#ifndef PPR_NT_OUT
-#define PPR_NT_OUT 0
-#endif
-#ifndef PPR_PRIO_B
-#define PPR_PRIO_B 0  /* wave priority inside the non-matrix phases (experiment knob) */
-#endif
-#ifndef PPR_VALU_SPLIT
-#define PPR_VALU_SPLIT 0  /* 1: remainders of the bf16x3 split by vector instructions instead of the matrix pipe (experiment knob) */
-#endif
+// alternating in one GPU call).  So is the backward chain's dE.  e' (`out`, re-read by the next launch) stays a plain store (st4).
 #define PPR_TILE_PIECES (12 * 1024)
 #define PPR_IMG (PPR_R * PPR_TILE_PIECES)
 #define PPR_OFF_P 0
@@ -109,11 +85,7 @@ extern "C" int mgn_debug_ppr_timeline(unsigned long long* out, int* n) {
 #define PPR_TL_DUMP() ((void)0)
 #endif
 
-template <bool NT>
-__device__ __forceinline__ void ppr_st4(float* p, f32x4 v) {
-  if (NT) __builtin_nontemporal_store(v, (g_f32x4*)p);
-  else *(g_f32x4*)p = v;
-}
+__device__ __forceinline__ void ppr_st4_nt(float* p, f32x4 v) { __builtin_nontemporal_store(v, (g_f32x4*)p); }
 // phase boundary: LDS writes of this wave are done, nothing is scheduled across it
 __device__ __forceinline__ void ppr_barrier() {
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -121,21 +93,6 @@ __device__ __forceinline__ void ppr_barrier() {
   __builtin_amdgcn_s_barrier();
   __builtin_amdgcn_sched_barrier(0);
   asm volatile("" ::: "memory");
-}
-// One LDS-DMA of 1 KB with a per-lane 64-bit address: lane L fetches 16 bytes at gaddr(L) into LDS byte lds_addr + 16 L
-// (see glds16 of mgn_kernels.hip for the M0 handling; the destination must be wave-uniform)
-__device__ __forceinline__ void glds16v(const void* gaddr, unsigned lds_addr) {
-  unsigned keep;
-  asm volatile(
-      "s_nop 4\n\t"
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, off\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(gaddr), "s"(lds_addr)
-      : "memory");
 }
 
 // make a per-lane value opaque: what is derived from it inside the group loop is re-derived there (one or two instructions)
@@ -170,9 +127,12 @@ __device__ __forceinline__ void glds16x2(const float* sbase, unsigned voff0, uns
 template <bool TRAIN, bool XCD>
 __global__ void __launch_bounds__(512, 2) k_edge_fwd_ppr(const mgn_mlp_fwd_args a) {
   constexpr int H = 128, R = PPR_R;
+  // GH1: the gathered rows Pd[dst] / Ps[src] of a group are asked for by the SECOND half's waves, in their first boundary phase -- one phase
+  // earlier than the first half could (the buffer is free as soon as the first half's unit-0 boundary has read it), and waited for at the
+  // end of their epilogue phase: 2.5 phases to land instead of 1.5, and the first half's heaviest boundary loses four LDS-DMA pairs
   // (measured in situ, alternating: inference 132-134 against 134-140 us with the gathers asked for by the second half, training mode
   // 201-206 against 193-197 us -- its extra scalar state spills two weight fragments -- so the training-mode instance keeps them in the first half)
-  constexpr bool GH1 = (PPR_GATHER_H1 != 0) && !TRAIN;
+  constexpr bool GH1 = !TRAIN;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   lds_char* sm = (lds_char*)smem;
   const int lane = threadIdx.x & 63;
@@ -196,17 +156,11 @@ __global__ void __launch_bounds__(512, 2) k_edge_fwd_ppr(const mgn_mlp_fwd_args 
   const int ng = g1 - g0;
 
   // ---- the wave's weights: units 2h, 2h+1 (back to back with unit 0: checked by the launcher), blocks 2w, 2w+1
-#ifdef PPR_EXP_HALFW
-  u32x4 W[1][3][2][4];
-#define PPR_NU 1
-#else
   u32x4 W[2][3][2][4];  // [unit of the half][piece][block][K-slice]
-#define PPR_NU 2
-#endif
   {
     const char* wb = (const char*)a.wpk[0] + (size_t)(2 * h) * MGN_WPACK_BYTES + (size_t)(2 * w) * 1024 + 16u * lane;
 #pragma unroll
-    for (int u = 0; u < PPR_NU; ++u)
+    for (int u = 0; u < 2; ++u)
 #pragma unroll
       for (int p = 0; p < 3; ++p)
 #pragma unroll
@@ -299,26 +253,6 @@ __global__ void __launch_bounds__(512, 2) k_edge_fwd_ppr(const mgn_mlp_fwd_args 
   // instructions cost the wave ~190 cycles each (tools/timeline_ppr.py); between the conversions they queue behind nothing
   auto put_slices = [&](f32x4 (&b)[R][2], unsigned img, auto hook, int k0) {
     lds_char* o = ppr_lds(img) + (w * 3) * 1024;
-#if PPR_VALU_SPLIT
-#pragma unroll
-    for (int p = 0; p < 3; ++p) {
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-        const u32x4 x = pk4(b[r][0], b[r][1]);
-        *(__attribute__((address_space(3))) u32x4*)(o + r * PPR_TILE_PIECES + p * 1024) = x;
-        if (p < 2) {
-#pragma unroll
-          for (int q = 0; q < 2; ++q) {
-            b[r][q][0] -= bf_lo(x[2 * q]), b[r][q][1] -= bf_hi(x[2 * q]);
-            b[r][q][2] -= bf_lo(x[2 * q + 1]), b[r][q][3] -= bf_hi(x[2 * q + 1]);
-          }
-        }
-        hook(k0 + p * R + r);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-    return;
-#endif
     SplitSel S;  // (two LDS reads instead of ~22 vector instructions; not kept: 8 registers that the matrix phases need)
     {
       lds_char* sp = ppr_lds(sm0 + PPR_OFF_SEL + 16u * ppr_opaque(lane));
@@ -345,9 +279,6 @@ __global__ void __launch_bounds__(512, 2) k_edge_fwd_ppr(const mgn_mlp_fwd_args 
   // ---- boundary after a hidden layer l = 0..2 (its pre-activations are in acc): ReLU, saves, mask, operand of the next unit;
   // hook(0 .. 5R - 1)
   auto post_hidden = [&](int l, int gi, unsigned img_out, bool add_gathered, auto hook) {
-#ifdef PPR_EXP_NOPOST
-    return;
-#endif
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       if (add_gathered) {  // z0 = W_e e + b0 + Pd[dst] + Ps[src] (in k_mlp_fwd_x6's order of the two additions)
@@ -382,7 +313,7 @@ __global__ void __launch_bounds__(512, 2) k_edge_fwd_ppr(const mgn_mlp_fwd_args 
         const unsigned ro = row_off(tile_row0(gi, r));
         const float* sh = pick3(a.saveH[0], a.saveH[1], a.saveH[2], l);
 #pragma unroll
-        for (int q = 0; q < 2; ++q) ppr_st4<PPR_NT_SAVES != 0>(at(sh, ro, q), acc[r][q]);
+        for (int q = 0; q < 2; ++q) ppr_st4_nt(at(sh, ro, q), acc[r][q]);
         // word g of row m holds bit 4 ib + e for feature 16 ib + 4 g + e: this wave's blocks are byte w of the word (byte 16 m + 4 g + w)
         const uint32_t* smk = pick3(a.saveM[0], a.saveM[1], a.saveM[2], l);
         *(__attribute__((address_space(1))) unsigned char*)((char*)smk + (size_t)(((ro >> 9) << 4) + 4 * g + w)) = (unsigned char)bits;
@@ -504,9 +435,6 @@ __global__ void __launch_bounds__(512, 2) k_edge_fwd_ppr(const mgn_mlp_fwd_args 
   // epilogue of group gi (z in acc, the rows' square sums in LDS): RMSNorm (reference epsilon placement), residual, stores, and the
   // fused aggregation of y over runs of equal keys (seg_scan_store<true> of mgn_x6.inc, this wave's two blocks)
   auto epilogue = [&](int gi) {
-#ifdef PPR_EXP_NOEPI
-    return;
-#endif
     // stage by stage over the R tiles (their dependent chains -- LDS read, square root, two divisions, products, four scan steps --
     // cover each other: tile after tile the phase took 1 400-1 800 cycles per tile)
     const unsigned EO = eoff(gi);
@@ -531,10 +459,10 @@ __global__ void __launch_bounds__(512, 2) k_edge_fwd_ppr(const mgn_mlp_fwd_args 
 #pragma unroll
       for (int r = 0; r < R; ++r) {
         const f32x4 u = acc[r][q] * inv[r];
-        if (TRAIN) ppr_st4<PPR_NT_SAVES != 0>(at(a.saveU, ro[r], q), u);
+        if (TRAIN) ppr_st4_nt(at(a.saveU, ro[r], q), u);
         y[r][q] = sc4 * u;
         const f32x4 er = *(lds_cf32x4*)(ppr_lds((q ? lq1 : lq0) + EO) + r * 8192);
-        ppr_st4<PPR_NT_OUT != 0>(at(a.out, ro[r], q), er + y[r][q]);
+        st4(at(a.out, ro[r], q), er + y[r][q]);
       }
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -619,7 +547,6 @@ __global__ void __launch_bounds__(512, 2) k_edge_fwd_ppr(const mgn_mlp_fwd_args 
     PPR_STAMP(2);
     ppr_barrier();
     PPR_STAMP(3);
-    if (PPR_PRIO_B) __builtin_amdgcn_s_setprio(PPR_PRIO_B);
     // boundary of layer 2h; spread through it: h = 0 the next group's e rows (R LDS-DMA pairs), GH1: h = 1 the gathered rows of group
     // gi + 2 (2R pairs) -- TRAIN: all issued before the boundary's first store
     if (h) load_keys(gi);
@@ -647,14 +574,13 @@ __global__ void __launch_bounds__(512, 2) k_edge_fwd_ppr(const mgn_mlp_fwd_args 
         if (r < R && (TRAIN || (k & 1) == 0)) dma_e2(d, gi + 1, r);
       });  // TRAIN: 6 stores
     }
-    if (PPR_PRIO_B) __builtin_amdgcn_s_setprio(0);
     // ================= second unit of the half (h = 0: layer 1; h = 1: layer 3)
     PPR_STAMP(4);
     ppr_barrier();
     PPR_STAMP(5);
     i32x4 iv[R][2];  // !GH1, h = 0: the next group's gather indices -- scalar loads issued here, used by the boundary after this matrix phase
     if (!GH1 && h == 0) load_gidx(gi + 1, iv);
-    matrix(W[PPR_NU - 1], 1, pB);
+    matrix(W[1], 1, pB);
     // h = 0: the next group's e rows, asked for in the boundary phase, have landed: their LDS-DMAs were issued before the boundary's six
     // stores (TRAIN), which may stay in flight.  (GH1: the second half's gather pairs have until the end of its epilogue phase.)
     if (h == 0) {
@@ -677,7 +603,6 @@ __global__ void __launch_bounds__(512, 2) k_edge_fwd_ppr(const mgn_mlp_fwd_args 
     PPR_STAMP(6);
     ppr_barrier();
     PPR_STAMP(7);
-    if (PPR_PRIO_B) __builtin_amdgcn_s_setprio(PPR_PRIO_B);
     if (h == 0) {
       // boundary of layer 1 -> Qin, then the next group's e rows -> P; the next group's gathered rows (4R LDS-DMA instructions)
       // spread through both
@@ -708,7 +633,6 @@ __global__ void __launch_bounds__(512, 2) k_edge_fwd_ppr(const mgn_mlp_fwd_args 
         else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
       }
     }
-    if (PPR_PRIO_B) __builtin_amdgcn_s_setprio(0);
   }
   if (h == 0) {  // five more phases: the other half drains its pipeline
 #pragma unroll 1
@@ -891,9 +815,6 @@ __global__ void __launch_bounds__(512, 2) k_edge_bwd_ppr(const mgn_mlp_bwd_args 
   // boundary of a chain unit: dz_{l-1} = acc masked by the ReLU bits of layer l's input (mask layer ml = l - 1), stored to dZ[ml],
   // split into the operand of the next unit
   auto post_masked = [&](int ml, int gi, unsigned img_out) {
-#ifdef PPB_EXP_NOPOST
-    return;
-#endif
     float* dzp = pick3(a.dZ[0], a.dZ[1], a.dZ[2], ml);
 #pragma unroll
     for (int r = 0; r < R; ++r) {
@@ -910,7 +831,7 @@ __global__ void __launch_bounds__(512, 2) k_edge_bwd_ppr(const mgn_mlp_bwd_args 
         }
       const unsigned ro = row_off(tile_row0(gi, r));
 #pragma unroll
-      for (int q = 0; q < 2; ++q) ppr_st4<PPB_NT_DZ != 0>(at(dzp, ro, q), acc[r][q]);
+      for (int q = 0; q < 2; ++q) ppr_st4_nt(at(dzp, ro, q), acc[r][q]);
       __builtin_amdgcn_sched_barrier(0);
     }
     put_slices(acc, img_out);
@@ -954,9 +875,6 @@ __global__ void __launch_bounds__(512, 2) k_edge_bwd_ppr(const mgn_mlp_bwd_args 
   // everything of group gi that the RMSNorm backward and the masks need: dOut, dOut2[idx2], U rows; mask words (wave w < 3: layer w);
   // rms (wave 3)
   auto dma_rows = [&](int gi) {
-#ifdef PPB_EXP_NODMA
-    return;
-#endif
     const int gc = clampg(gi);
     const DmaLane d = dma_lane();
     i32x4 iv[R];
@@ -1003,9 +921,6 @@ __global__ void __launch_bounds__(512, 2) k_edge_bwd_ppr(const mgn_mlp_bwd_args 
   };
   // ---- h = 1: the partial row products <scale dY, U> of group gi (this wave's 32 features) -> LDS, and its share of dscale
   auto row_dots = [&](int gi) {
-#ifdef PPB_EXP_NODOTS
-    return;
-#endif
     // block by block (4 accumulators of dscale live at a time, not 8: with both blocks in flight the phase spilled five weight
     // fragments, whose reloads in the matrix phase wait for every store in flight)
     const float ones[4] = {1.f, 1.f, 1.f, 1.f};
@@ -1027,12 +942,8 @@ __global__ void __launch_bounds__(512, 2) k_edge_bwd_ppr(const mgn_mlp_bwd_args 
         const f32x4 u = *(lds_cf32x4*)(lp + 2 * R * 8192);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-#ifndef PPB_EXP_NOVS
           vs[e] = fmaf(dy[e] * keep[r], u[e], vs[e]);
-#endif
-#ifndef PPB_EXP_NODP
           dp[r] = fmaf(sc[e] * dy[e], u[e], dp[r]);
-#endif
         }
         // (pinned HERE: machine sinking otherwise moves the row product down to its use after the scan, and the rows it reads stay
         // live across it -- five weight fragments spilled)
@@ -1041,9 +952,7 @@ __global__ void __launch_bounds__(512, 2) k_edge_bwd_ppr(const mgn_mlp_bwd_args 
       }
       // sum over the 16 rows (an inclusive DPP scan leaves the total in lane 15 of every row of lanes), then onto the wave's own
       // accumulators in LDS (no other wave touches them)
-#ifndef PPB_EXP_NOSCAN
       pp_seg_scan_blk(vs, ones);
-#endif
       if (c == 15) {
         __attribute__((address_space(3))) f32x4* dp4 = (__attribute__((address_space(3))) f32x4*)(sm + PPB_OFF_DSC + 64 * (2 * w + q) + 16 * g);
         *dp4 = *dp4 + vs;
@@ -1052,20 +961,13 @@ __global__ void __launch_bounds__(512, 2) k_edge_bwd_ppr(const mgn_mlp_bwd_args 
     }
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-#ifdef PPB_EXP_SHFL
-      const float t = rowsum4(dp[r]);
-#else
       const float t = pp_rowsum4(dp[r]);
-#endif
       if (g == 0) *(__attribute__((address_space(3))) float*)(sm + PPB_OFF_DOT + (r * 16 + c) * 16 + 4 * w) = t;
     }
   };
   // ---- h = 0: dz3 of group gi (this wave's 32 features) from the landed rows and the row products: stored to dZ[3], split -> P
   //      dz = g / (rms + eps) - u <g, u> / (H rms),  g = scale dY
   auto form_dz3 = [&](int gi) {
-#ifdef PPB_EXP_NODZ3
-    return;
-#endif
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       const int cc = ppr_opaque(lane) & 15;
@@ -1082,7 +984,7 @@ __global__ void __launch_bounds__(512, 2) k_edge_bwd_ppr(const mgn_mlp_bwd_args 
         const f32x4 u = *(lds_cf32x4*)(lp + 2 * R * 8192);
         const f32x4 sc = *(lds_cf32x4*)(sm + PPB_OFF_CST + 64 * (2 * w + q) + 16 * g);
         acc[r][q] = (sc * dy) * inv - u * k2;
-        ppr_st4<PPB_NT_DZ != 0>(at(a.dZ[3], ro, q), acc[r][q]);
+        ppr_st4_nt(at(a.dZ[3], ro, q), acc[r][q]);
         __builtin_amdgcn_sched_barrier(0);
       }
     }
@@ -1155,7 +1057,7 @@ __global__ void __launch_bounds__(512, 2) k_edge_bwd_ppr(const mgn_mlp_bwd_args 
         for (int r = 0; r < R; ++r) {
           const unsigned ro = row_off(tile_row0(gi, r));
 #pragma unroll
-          for (int q = 0; q < 2; ++q) ppr_st4<PPB_NT_DE != 0>(at(a.dIn[0], ro, q), *(lds_cf32x4*)(ppr_lds(q ? lq1 : lq0) + RO + r * 8192) + acc[r][q]);
+          for (int q = 0; q < 2; ++q) ppr_st4_nt(at(a.dIn[0], ro, q), *(lds_cf32x4*)(ppr_lds(q ? lq1 : lq0) + RO + r * 8192) + acc[r][q]);
         }
       }
     }

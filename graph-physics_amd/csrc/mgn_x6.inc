@@ -30,12 +30,6 @@ typedef __attribute__((address_space(3))) const u32x4 lds_cu32x4;
 #define X6_RING 3
 #define X6_FWD_LDS_BYTES(NW) (((NW) == 8 ? 6 : 3) * X6_QBYTES + 5 * 512)
 #define X6_MAX_UNITS 8
-#ifndef MGN_GQ_DB
-#define MGN_GQ_DB 0  /* experiment: every weight fragment of gemm_q double buffered (measured neutral: 76.6 / 75.8 against 77.0 / 76.1 steps/s) */
-#endif
-#ifndef X6_FWD_NW_LARGE
-#define X6_FWD_NW_LARGE 4  /* waves per workgroup of the forward kernel on large M (experiment: 8) */
-#endif
 
 #define MFMA_BF(a, b, c) \
   __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, (a)), __builtin_bit_cast(bf16x8, (b)), (c), 0, 0, 0)
@@ -64,14 +58,11 @@ __device__ __forceinline__ void split2(float a, float b, u32& q1, u32& q2, u32& 
 // (cvt, shift, sub, cvt, shift, sub, cvt) would otherwise be executed pair after pair,
 // latency-bound (measured ~2000 cycles per tile against ~450 issue cycles).
 // TERMS == 1 (bf16 matrix mode): only the leading piece is made and used.
-// [r4] MGN_SPLIT_MFMA (default on): the remainders x - bf16(x) come from the MATRIX pipe.  With S0 / S1 = minus the selector of
+// [r4] The remainders x - bf16(x) come from the MATRIX pipe.  With S0 / S1 = minus the selector of
 // a K-slice's first / second 16 features (an A operand of -1.0 and 0.0: lane (c, g) holds -1 at element i where
 // 16 (i >> 2) + 4 g + (i & 3) == c [+ 16]), S . piece + x is ONE MFMA per 16 x 16 block, exact (one non-zero product per
 // output, the sum is representable) and already in the T-layout: 12 conversions + 4 MFMAs per K-slice instead of 44 VALU
 // instructions (shift / mask / two subtractions per value pair).  Same pieces bit for bit.
-#ifndef MGN_SPLIT_MFMA
-#define MGN_SPLIT_MFMA 1
-#endif
 struct SplitSel {
   u32x4 s0, s1;
 };
@@ -112,14 +103,12 @@ __device__ __forceinline__ void split_pair_mfma(const f32x4& b0, const f32x4& b1
 
 template <int TERMS, bool MF = true>
 __device__ __forceinline__ void split_tile(const f32x4 (&v)[8], u32x4 (&xs)[4][3]) {
-#if MGN_SPLIT_MFMA
   if (TERMS != 1 && MF) {  // (MF = false: instances that would spill with the MFMA form's longer-lived remainders)
     const SplitSel S = split_sel();
 #pragma unroll
     for (int j = 0; j < 4; ++j) split_pair_mfma(v[2 * j], v[2 * j + 1], xs[j], S);
     return;
   }
-#endif
   u32 q1[16], q2[16], q3[16];
   float ra[16], rb[16];
 #pragma unroll
@@ -241,26 +230,19 @@ __device__ __forceinline__ void gemm_q(f32x4 (&acc)[8], const u32x4 (&x)[3], lds
 #pragma unroll
         for (int q = 0; q < 2; ++q) w1[(s + 1) & 1][q] = *(lds_cu32x4*)(wl + (2 * (s + 1) + q) * 1024);
       }
-#ifndef X6_B16_DMA_AT0
-#define X6_B16_DMA_AT0 1   /* one-term quarters are short (8 MFMAs): request the whole share of the quarter two ahead at step 0 instead of
-                              spread over steps 0..2 -- half an iteration more lead on the L2 -> LDS latency (the drain's count only gets
-                              more conservative: hook loads of steps 0..2 are now younger than the pieces and still counted as older).
-                              configs[2] step 14.71-14.76 -> 14.43-14.54 ms, alternating */
-#endif
-      if (X6_B16_DMA_AT0 && PPW != 6) {
+      // one-term quarters are short (8 MFMAs): request the whole share of the quarter two ahead at step 0 instead of spread over
+      // steps 0..2 -- half an iteration more lead on the L2 -> LDS latency (the drain's count only gets more conservative: hook
+      // loads of steps 0..2 are now younger than the pieces and still counted as older).  configs[2] step 14.71-14.76 ->
+      // 14.43-14.54 ms, alternating.  (PPW == 6, the backward chain: a pair of pieces per step, as in the six-term form.)
+      if (PPW != 6) {
         if (s == 0) {
 #pragma unroll
           for (int i = 0; i < PPW; ++i) dmaq_issue(job, i, lane16);
         }
       } else if (s < 3) {
-        if (PPW == 6) {
-          if (s == 0) dmaq_issue2<0>(job, lane16);
-          else if (s == 1) dmaq_issue2<1>(job, lane16);
-          else dmaq_issue2<2>(job, lane16);
-        } else {
-#pragma unroll
-          for (int i = s * PPW / 3; i < (s + 1) * PPW / 3; ++i) dmaq_issue(job, i, lane16);
-        }
+        if (s == 0) dmaq_issue2<0>(job, lane16);
+        else if (s == 1) dmaq_issue2<1>(job, lane16);
+        else dmaq_issue2<2>(job, lane16);
       }
       late(s);
       __builtin_amdgcn_sched_barrier(0);
@@ -273,50 +255,6 @@ __device__ __forceinline__ void gemm_q(f32x4 (&acc)[8], const u32x4 (&x)[3], lds
   // term order w3x1, w2x2, w2x1, w1x3, w1x2, w1x1 (roughly ascending magnitude): the w3 / w2
   // fragments are dead after one / three terms and are refilled in place for the next pair;
   // only w1 is double buffered.
-#if MGN_GQ_DB
-  // experiment (-DMGN_GQ_DB=1): all three pieces double buffered, the next step's six fragments requested at the head of the step
-  // (a dependent ds_read_b128 beside a partner wave that streams MFMAs takes ~350 cycles, tools/coissue_probe.hip; the in-place
-  // refills below are requested 8-10 MFMAs = 130-160 cycles before their first use).  PPW == 6 (backward chain): registers do not allow it.
-  if constexpr (PPW != 6) {
-    u32x4 wb[2][3][2];
-    lds_char* wl = wq + lane16;
-#pragma unroll
-    for (int pc = 0; pc < 3; ++pc)
-#pragma unroll
-      for (int q = 0; q < 2; ++q) wb[0][pc][q] = *(lds_cu32x4*)(wl + pc * 8192 + q * 1024);
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      const int nb = (2 * (s + 1)) * 1024;
-      if (s + 1 < 4) {
-#pragma unroll
-        for (int pc = 0; pc < 3; ++pc)
-#pragma unroll
-          for (int q = 0; q < 2; ++q) wb[(s + 1) & 1][pc][q] = *(lds_cu32x4*)(wl + pc * 8192 + nb + q * 1024);
-      }
-      if (s < 3) {
-#pragma unroll
-        for (int i = s * PPW / 3; i < (s + 1) * PPW / 3; ++i) dmaq_issue(job, i, lane16);
-      }
-      late(s);
-      __builtin_amdgcn_sched_barrier(0);
-      const int b = s & 1;
-#pragma unroll
-      for (int q = 0; q < 2; ++q) acc[2 * s + q] = MFMA_BF(wb[b][2][q], x[0], acc[2 * s + q]);
-#pragma unroll
-      for (int q = 0; q < 2; ++q) acc[2 * s + q] = MFMA_BF(wb[b][1][q], x[1], acc[2 * s + q]);
-#pragma unroll
-      for (int q = 0; q < 2; ++q) acc[2 * s + q] = MFMA_BF(wb[b][1][q], x[0], acc[2 * s + q]);
-#pragma unroll
-      for (int q = 0; q < 2; ++q) acc[2 * s + q] = MFMA_BF(wb[b][0][q], x[2], acc[2 * s + q]);
-#pragma unroll
-      for (int q = 0; q < 2; ++q) acc[2 * s + q] = MFMA_BF(wb[b][0][q], x[1], acc[2 * s + q]);
-#pragma unroll
-      for (int q = 0; q < 2; ++q) acc[2 * s + q] = MFMA_BF(wb[b][0][q], x[0], acc[2 * s + q]);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    return;
-  }
-#endif
   u32x4 w3[2], w2[2], w1[2][2];
   lds_char* wl = wq + lane16;
 #pragma unroll
@@ -392,10 +330,6 @@ __device__ __forceinline__ T pick8(T a0, T a1, T a2, T a3, T a4, T a5, T a6, T a
 // Wait until at most `n` (floored to a supported immediate) of the youngest VMEM operations are
 // outstanding.  vmcnt retires in issue order: everything older than the n youngest has landed.
 __device__ __forceinline__ void drain_allow(int n) {
-#ifdef MGN_EXP_NODRAIN  // timing experiment only (results are garbage): what the counted waits cost
-  (void)n;
-  return;
-#endif
   if (n >= 38)
     dma_drain_counted<38>();
   else if (n >= 30)
@@ -548,38 +482,9 @@ __device__ __forceinline__ void ld2(f32x4 (&dst)[8], const float* rowp, int s, i
   n += 2;
 }
 
-// Chip-level phase stagger: all workgroups start together and run the same schedule, so their
-// store bursts (8 KB per wave and unit) hit HBM at the same moments and the compute phases leave
-// it idle.  Delaying workgroup b by (b mod 4) quarter-units spreads the bursts.
-#ifdef MGN_EXP_PAIR_STAGGER
-// experiment (tools/stagger_sweep.py): the second dispatch round (blocks >= gridDim/2 share their CUs with the first:
-// tools/timeline_x6.py census) starts `g_pair_stagger` x 10 ns late, so the two waves of a SIMD are out of phase
-__device__ int g_pair_stagger = 0;
-extern "C" int mgn_debug_set_stagger(int ticks) { return hipMemcpyToSymbol(HIP_SYMBOL(g_pair_stagger), &ticks, sizeof(int)) != hipSuccess; }
-#endif
-__device__ __forceinline__ void x6_stagger() {
-#ifdef MGN_EXP_PAIR_STAGGER
-  const int w = g_pair_stagger;
-  if (w > 0 && blockIdx.x * 2 >= gridDim.x) {
-    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-    while (__builtin_amdgcn_s_memrealtime() - t0 < (unsigned long long)w) __builtin_amdgcn_s_sleep(8);
-  }
-#endif
-#ifdef MGN_EXP_STAGGER4
-  const unsigned long long wait = (unsigned long long)(blockIdx.x & 3) * MGN_EXP_STAGGER4;
-  const unsigned long long t0 = __builtin_readcyclecounter();
-  while (__builtin_readcyclecounter() - t0 < wait) __builtin_amdgcn_s_sleep(16);
-#endif
-}
-
-// Walk of the row tiles by a persistent workgroup.  Default: tile b, b + gridDim, ... (neighbouring tiles run
-// at the same time on neighbouring workgroups = on all 8 XCDs).  -DMGN_XCD_WALK builds the XCD-aware
-// variant instead: workgroup b runs on XCD b % 8 (each XCD has its own 4 MB L2), XCD x owns the contiguous
-// tile range [x*C, (x+1)*C), C = ceil(ntiles / 8), and its gridDim/8 workgroups stride through it, so the
-// gathered node rows an L2 sees shrink to 1/8 (2 of the 16 meshes: 2 MB of projections).  MEASURED: 1 %
-// slower on the bench workload (71.4 vs 72.2 steps/s, alternating A/B in one GPU call; edge forward 247 vs
-// 242 us) -- the gathers are not what bounds the kernel (its loads cost 6-10 us of 230) and a contiguous
-// chunk per XCD concentrates each XCD's streaming traffic on fewer memory channels at a time.
+// Walk of the row tiles by a persistent workgroup: tile b, b + gridDim, ... (neighbouring tiles run at the same
+// time on neighbouring workgroups = on all 8 XCDs).  An XCD-aware walk (a contiguous eighth of the tiles per XCD)
+// was measured 1 % slower: DESIGN.md section 9.
 struct TileWalk {
   long first, end, stride;  // this workgroup's tiles: first, first + stride, ... < end
   long count;
@@ -587,19 +492,7 @@ struct TileWalk {
 __device__ __forceinline__ TileWalk tile_walk(long ntiles) {
   TileWalk w;
   const unsigned G = gridDim.x, b = blockIdx.x;
-#ifdef MGN_XCD_WALK  // opt-in build flag: measured 1 % SLOWER than the plain walk on the bench workload (A/B, 3 + 3 runs)
-  if ((G & 7u) == 0 && ntiles >= 64) {
-#else
-  if (false) {
-#endif
-    const long C = (ntiles + 7) / 8, x = b & 7u, per = G >> 3;
-    const long lo = x * C;
-    w.end = (lo + C < ntiles) ? lo + C : ntiles;
-    w.first = lo + (b >> 3);
-    w.stride = per;
-  } else {
-    w.first = b, w.end = ntiles, w.stride = G;
-  }
+  w.first = b, w.end = ntiles, w.stride = G;
   w.count = (w.first < w.end) ? (w.end - w.first + w.stride - 1) / w.stride : 0;
   return w;
 }
@@ -716,7 +609,6 @@ __global__ void __launch_bounds__(64 * NW, (NW == 6 ? 3 : 2)) k_mlp_fwd_x6(const
   long tile = tw.first;
   if (tw.count == 0) return;
   const long my_tiles = tw.count;
-  x6_stagger();
   const int GL = NPH + NLL - 1;
   const int G = GL + NPOST;
   const char *U0 = (const char*)a.wpk[0], *U1 = (const char*)a.wpk[1], *U2 = (const char*)a.wpk[2], *U3 = (const char*)a.wpk[3];
@@ -819,9 +711,6 @@ __global__ void __launch_bounds__(64 * NW, (NW == 6 ? 3 : 2)) k_mlp_fwd_x6(const
       TL_STAMP(3);
       __syncthreads();  // quarter landed everywhere; the slot of two quarters ago is free again
       TL_STAMP(4);
-#ifdef MGN_EXP_PRIO
-      __builtin_amdgcn_s_setprio(0);
-#endif
       const DmaQ job = next_job();
       const int before = qs.young;
       qs.young = 0;
@@ -841,9 +730,6 @@ __global__ void __launch_bounds__(64 * NW, (NW == 6 ? 3 : 2)) k_mlp_fwd_x6(const
       }
       TL_STAMP(6);
     }
-#ifdef MGN_EXP_PRIO
-    __builtin_amdgcn_s_setprio(3);  // split / epilogue phases: the serial part of the wave
-#endif
   };
 
   for (; tile < tw.end; tile += tw.stride) {
@@ -1156,7 +1042,6 @@ __global__ void __launch_bounds__(256, 2) k_mlp_bwd_x6(const mgn_mlp_bwd_args a)
   const TileWalk tw = tile_walk(ntiles);
   long tile = tw.first;
   const long my_tiles = tw.count;
-  x6_stagger();
   // optional front stage (fusion of the dX launch of round i with the node chain of round i-1):
   //   dY[m] = front_resid[m] + sum_p Wfront_p . front_src[p][m]   (stored to front_out)
   // its n_front units lead the stream; `src_rows` is what the tile's first operand rows are
@@ -1531,17 +1416,7 @@ __global__ void __launch_bounds__(256, 2) k_mlp_bwd_x6(const mgn_mlp_bwd_args a)
 // workgroups per CU do not have).
 // [r4] the same for rows stored as bf16 (256 bytes; the two-byte saves of precision == 2): a 32-row tile is 8 pieces of 4 rows, two per
 // wave; 16-byte chunk p of row r holds global chunk p ^ (4 * ((r >> 3) & 1)), so the 2-byte reads of rows 8g + t (lane groups of 32
-// = two values of g) fall 64 bytes apart
-__device__ __forceinline__ void dma_row_piece4_bf(const uint16_t* __restrict__ X, long row0, long M, unsigned lds0, int wv, int lane, int i) {
-  const int q = 2 * wv + i;
-  const int r = 4 * q + (lane >> 4);
-  long row = row0 + r;
-  row = row < M ? row : M - 1;
-  const int gch = (lane & 15) ^ (4 * ((r >> 3) & 1));
-  const unsigned voff = (unsigned)((row - row0) * 256 + 16 * gch);
-  glds16(uniform_ptr((const float*)(X + row0 * 128)), voff, lds0 + q * 1024);
-}
-
+// = two values of g) fall 64 bytes apart (dma_op of k_wgrad_x6)
 __device__ __forceinline__ void dma_row_piece8(const float* __restrict__ X, long row0, long M, unsigned lds0, int wv, int lane, int i) {
   const int q = 4 * wv + i;
   const int r = 2 * q + (lane >> 5);
@@ -1577,11 +1452,8 @@ __device__ __forceinline__ void split8(const float (&v)[8], u32x4& p1, u32x4& p2
 // (rows 8g..8g+7 of one feature) ARE the B operand of a K = 32 MFMA; seen as two 16 x 16 tiles in the C/D layout (rows
 // 8g'+0..3 and rows 8g'+4..7, column = the feature) they are also its C input, so  v - bf16(v) = Sel . piece + v  with
 // Sel_h[i][k] = -1 where k = 8 (i >> 2) + 4 h + (i & 3): lane (i, g) holds -1 at element 4 h + (i & 3) when g == i >> 2.
-// 12 conversions + 4 MFMAs per block instead of 44 VALU instructions (the kernel was VALU-bound: ~500 VALU + 96 MFMA per tile
-// and wave).
-#ifndef MGN_WGRAD_SPLIT_MFMA
-#define MGN_WGRAD_SPLIT_MFMA 0  /* measured neutral to slightly slower (186 vs 180-186 us per round, tools/kbench_wgrad.py): 32 more MFMAs per tile make the kernel matrix-bound where it was VALU-bound */
-#endif
+// 12 conversions + 4 MFMAs per block instead of 44 VALU instructions.  Used by the producers of k_wgrad_pc; k_wgrad_x6 keeps the
+// vector form split8 (the matrix-pipe form made it matrix-bound where it was VALU-bound: DESIGN.md section 9).
 struct WgSel {
   u32x4 s0, s1;
 };
@@ -1602,15 +1474,6 @@ __device__ __forceinline__ WgSel wg_sel(int c, int g) {
   }
   return S;
 }
-__device__ __forceinline__ void split8_mfma(const float (&v)[8], u32x4& p1, u32x4& p2, u32x4& p3, const WgSel& S) {
-  const f32x4 lo = {v[0], v[1], v[2], v[3]}, hi = {v[4], v[5], v[6], v[7]};
-#pragma unroll
-  for (int h = 0; h < 4; ++h) p1[h] = pk_bf16(v[2 * h], v[2 * h + 1]);
-  const f32x4 r0 = MFMA_BF(S.s0, p1, lo), r1 = MFMA_BF(S.s1, p1, hi);
-  p2[0] = pk_bf16(r0[0], r0[1]), p2[1] = pk_bf16(r0[2], r0[3]), p2[2] = pk_bf16(r1[0], r1[1]), p2[3] = pk_bf16(r1[2], r1[3]);
-  const f32x4 t0 = MFMA_BF(S.s0, p2, r0), t1 = MFMA_BF(S.s1, p2, r1);
-  p3[0] = pk_bf16(t0[0], t0[1]), p3[1] = pk_bf16(t0[2], t0[3]), p3[2] = pk_bf16(t1[0], t1[1]), p3[3] = pk_bf16(t1[2], t1[3]);
-}
 
 template <int TERMS>
 __global__ void __launch_bounds__(256, 2) k_wgrad_x6(const WgradLaunch L) {
@@ -1628,6 +1491,8 @@ __global__ void __launch_bounds__(256, 2) k_wgrad_x6(const WgradLaunch L) {
   const long t0 = ntiles * wg / nwg, t1 = ntiles * (wg + 1) / nwg;
   const unsigned sm0 = __builtin_amdgcn_readfirstlane(lds_addr_of(sm));
   const int jb0 = 4 * (wv >> 1), kb0 = 4 * (wv & 1);
+  // (unused since the matrix-pipe split left this kernel for k_wgrad_pc, and dead after optimisation -- but without the line hipcc
+  // swaps two scalar instructions of k_wgrad_x6<1>; it goes with the next change that alters this kernel's code anyway)
   const WgSel wsel = wg_sel(c, g);
 
   f32x4 acc[4][4];
@@ -1699,25 +1564,8 @@ __global__ void __launch_bounds__(256, 2) k_wgrad_x6(const WgradLaunch L) {
             cs[o + q] += ((v[q][0] + v[q][1]) + (v[q][2] + v[q][3])) + ((v[q][4] + v[q][5]) + (v[q][6] + v[q][7]));
         }
       }
-#ifdef WGX_EXP_NOSPLIT  // timing experiment only (results are garbage): what the bf16x3 splits cost
-#pragma unroll
-      for (int q = 0; q < 2; ++q)
-#pragma unroll
-        for (int p3 = 0; p3 < 3; ++p3)
-#pragma unroll
-          for (int d = 0; d < 4; ++d) out[o + q][p3][d] = __builtin_bit_cast(u32, v[q][(d + p3) & 7]);
-#else
-#if MGN_WGRAD_SPLIT_MFMA
-      if (TERMS != 1) {
-        split8_mfma(v[0], out[o][0], out[o][1], out[o][2], wsel);
-        split8_mfma(v[1], out[o + 1][0], out[o + 1][1], out[o + 1][2], wsel);
-      } else
-#endif
-      {
-        split8(v[0], out[o][0], out[o][1], out[o][2]);
-        split8(v[1], out[o + 1][0], out[o + 1][1], out[o + 1][2]);
-      }
-#endif
+      split8(v[0], out[o][0], out[o][1], out[o][2]);
+      split8(v[1], out[o + 1][0], out[o + 1][1], out[o + 1][2]);
       __builtin_amdgcn_sched_barrier(0);  // (more pairs in flight cost registers: the kernel spills)
     };
     // bf16 rows: the eight values of a lane (rows 8g + t of one feature) are read as 2-byte halves straight into the packed operand
@@ -1760,13 +1608,8 @@ __global__ void __launch_bounds__(256, 2) k_wgrad_x6(const WgradLaunch L) {
       take(tb, kb0, false, bp, 2);
     }
     // six terms, smallest first; 16 independent accumulators per term
-#ifdef WGX_EXP_NOMFMA  // timing experiment only: one term of six
-#pragma unroll
-    for (int term = 5; term < 6; ++term) {
-#else
 #pragma unroll
     for (int term = (TERMS == 1 ? 5 : 0); term < 6; ++term) {
-#endif
       const int pa = (term == 0) ? 2 : (term == 1) ? 0 : (term == 2 || term == 3) ? 1 : 0;
       const int pb = (term == 0) ? 0 : (term == 1) ? 2 : (term == 2) ? 1 : (term == 3) ? 0 : (term == 4) ? 1 : 0;
 #pragma unroll
@@ -1814,7 +1657,7 @@ __global__ void __launch_bounds__(256, 2) k_wgrad_x6(const WgradLaunch L) {
 //     c ^ ((c >> 3) << 1) ^ (block & 1) -- the 8-lane groups of a ds_write_b128 (lanes q = 8k .. 8k + 7: two blocks x four
 //     16-byte column groups) then cover the 8 slots of a 128-byte bank row, and the 16-lane groups of a ds_read_b128 still see
 //     16 distinct slots (the swizzle permutes within {0-3}, {4-7}, {8-11}, {12-15}).
-//   * Measured on the way (tools/exp_wgrad.sh, bench shape, first version with two images and a consumer that read all 24 operand
+//   * Measured on the way (timing-experiment builds, bench shape, first version with two images and a consumer that read all 24 operand
 //     vectors after each barrier: 165 us against 183 us for k_wgrad_x6): without the splits 156-163 us, with two of six terms
 //     138 us, with cache-resident rows 123 us, with neither splits nor terms 137 us (the row stream + exchange alone), with none
 //     of the three 77 us.
@@ -1822,23 +1665,6 @@ __global__ void __launch_bounds__(256, 2) k_wgrad_x6(const WgradLaunch L) {
 #define WPC_IMG 49152
 #define WPC_NIMG 3
 #define WPC_LDS_BYTES (WPC_NIMG * WPC_IMG + 64)
-#ifndef WPC_FLAGS
-#define WPC_FLAGS 0   /* measured: 166-172 us against 163-165 us with the barrier (tools/exp_wgrad.sh FLAGS) -- the hand-over is not what the tile waits for */
-#endif
-#ifdef WPC_EXP_NOLOAD   /* timing experiment only: the same tiles over and over (cache-resident) */
-#define WPC_LOAD(next, same, raw) load_tile(same, raw)
-#else
-#define WPC_LOAD(next, same, raw) load_tile(next, raw)
-#endif
-#ifndef WPC_SPLIT_MFMA
-#define WPC_SPLIT_MFMA 1   /* remainders of the producers' splits from the matrix pipe (12 conversions + 4 MFMAs per 8 values instead of 44 vector instructions) */
-#endif
-#ifndef WPC_MFMA32
-#define WPC_MFMA32 0   /* measured slower: 174-181 us against 162-167 us (tools/exp_wgrad.sh), with either form of the producers' split */
-#endif
-#ifndef WPC_PRIO_P
-#define WPC_PRIO_P 1   /* producers: their loads / splits / writes go first, a consumer needs one issue slot per 16 cycles */
-#endif
 #ifdef MGN_TIMELINE
 // debug build only (tools/timeline_wpc.py): s_memtime stamps of wave 0 (a producer of A) and wave 4 (a consumer) of workgroup 0
 __device__ unsigned long long g_wpc_tl[2][2048];
@@ -1876,20 +1702,6 @@ __device__ __forceinline__ void wpc_barrier() {   // producers: their LDS writes
   __builtin_amdgcn_sched_barrier(0);
   asm volatile("" ::: "memory");
 }
-// [experiment, WPC_FLAGS=1] point-to-point hand-over instead of the per-tile s_barrier: producers post "tiles written" counters,
-// consumers post "images released" counters (eight ints behind the images); a side waits only when the OTHER side is really behind
-__device__ __forceinline__ int wpc_flags_min(unsigned addr) {
-  u32x4 v;
-  asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(addr) : "memory");
-  const int a = (int)v[0] < (int)v[1] ? (int)v[0] : (int)v[1], b = (int)v[2] < (int)v[3] ? (int)v[2] : (int)v[3];
-  return __builtin_amdgcn_readfirstlane(a < b ? a : b);
-}
-__device__ __forceinline__ void wpc_wait_ge(unsigned addr, int target) {
-  while (wpc_flags_min(addr) < target) __builtin_amdgcn_s_sleep(1);
-}
-__device__ __forceinline__ void wpc_post(unsigned addr, int value) {
-  asm volatile("ds_write_b32 %0, %1" ::"v"(addr), "v"(value) : "memory");
-}
 __device__ __forceinline__ void wpc_barrier_c() {  // consumers: reads in flight may cross it (see the image rotation above)
   __builtin_amdgcn_sched_barrier(0);
   __builtin_amdgcn_s_barrier();
@@ -1900,10 +1712,7 @@ __global__ void __launch_bounds__(512, 2) k_wgrad_pc(const WgradLaunch L) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   lds_char* sm = (lds_char*)smem;
   const int lane = threadIdx.x & 63;
-#ifndef WPC_SWAP
-#define WPC_SWAP 0   /* experiment: the consumers are the OLDER waves of each SIMD (the issue arbiter prefers the oldest ready wave) */
-#endif
-  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) ^ (WPC_SWAP ? 4 : 0);
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   int j = 0;
   while (j + 1 < L.njobs && (int)blockIdx.x >= L.wg0[j + 1]) ++j;
   const mgn_wgrad_job J = L.job[j];
@@ -1911,27 +1720,11 @@ __global__ void __launch_bounds__(512, 2) k_wgrad_pc(const WgradLaunch L) {
   const int wg = blockIdx.x - L.wg0[j];
   const long ntiles = (J.M + WG_TILE_ROWS - 1) / WG_TILE_ROWS;
   // tiles of this workgroup, by local index k in [0, n): interleaved (tile = wg + k * nwg: at any moment the workgroups of a job read
-  // one contiguous window of the operand rows, as a grid-stride copy does -- every memory channel carries the same share) or a
-  // contiguous range (WPC_INTERLEAVE=0)
-#ifndef WPC_INTERLEAVE
-#define WPC_INTERLEAVE 1
-#endif
-#if WPC_INTERLEAVE
+  // one contiguous window of the operand rows, as a grid-stride copy does -- every memory channel carries the same share)
   const long t0 = 0, t1 = (ntiles - wg + nwg - 1) / nwg;
   auto gtile = [&](long k) { return (long)wg + k * nwg; };
   const bool has_last = t1 > 0 && gtile(t1 - 1) == ntiles - 1;
-#else
-  const long tbase = ntiles * wg / nwg;
-  const long t0 = 0, t1 = ntiles * (wg + 1) / nwg - tbase;
-  auto gtile = [&](long k) { return tbase + k; };
-  const bool has_last = t1 > 0 && tbase + t1 == ntiles;
-#endif
   float* P = L.partial + (size_t)blockIdx.x * (128 * 128 + 128);
-  const unsigned flag_ready = __builtin_amdgcn_readfirstlane(lds_addr_of(sm)) + WPC_NIMG * WPC_IMG, flag_done = flag_ready + 16;
-#if WPC_FLAGS
-  if (threadIdx.x < 8) wpc_post(flag_ready + 4 * threadIdx.x, 0);
-  wpc_barrier();
-#endif
   WPC_TL_DECL();
 #ifdef MGN_TIMELINE
   if (tl_on_) g_wpc_tl[threadIdx.x >> 8][tl_n_++] = (__builtin_amdgcn_s_memrealtime() << 8) | 8;
@@ -1941,7 +1734,7 @@ __global__ void __launch_bounds__(512, 2) k_wgrad_pc(const WgradLaunch L) {
 
   if (wv < 4) {
     // ------------------------------------------------------------ producer
-    if (WPC_PRIO_P) __builtin_amdgcn_s_setprio(WPC_PRIO_P);
+    __builtin_amdgcn_s_setprio(1);  // producers: their loads / splits / writes go first, a consumer needs one issue slot per 16 cycles
     const int mat = wv >> 1, half = wv & 1;
     const int rg = lane >> 5, q = lane & 31;
     const int g = 2 * half + rg;
@@ -1954,23 +1747,15 @@ __global__ void __launch_bounds__(512, 2) k_wgrad_pc(const WgradLaunch L) {
     const bool want_db = (mat == 0) && (J.db != nullptr);
     f32x4 cs = {0.f, 0.f, 0.f, 0.f};
     f32x4 raw0[8], raw1[8], raw2[8], raw3[8];
-#if WPC_SPLIT_MFMA
     const WgSel wsel = wg_sel(lane & 15, lane >> 4);
-#endif
     // The pipelined loop runs over FULL tiles only and ALWAYS issues eight loads per tile (past the range it re-reads the last
     // full tile): the compiler counts the operations in flight, and a second load path or a conditionally issued group turns
     // every wait of the loop into vmcnt(~0) -- the two-tile prefetch would collapse (seen in the ISA).  A job's ragged last
     // tile is one un-pipelined step after the loop.
     const long tf = (has_last && (J.M % WG_TILE_ROWS) != 0) ? t1 - 1 : t1;
-    // (experiment, -DWPC_REVERSE=1: full tiles in DESCENDING order -- the backward chain wrote the dZ rows in ascending tile order just
-    // before this launch, so the END of the arrays would be what the 256 MiB Infinity Cache still holds.  Measured neutral: 202.6
-    // against 201.8-204.2 us per call in the training step, alternating.)
-#ifndef WPC_REVERSE
-#define WPC_REVERSE 0
-#endif
     auto load_tile = [&](long tile_, f32x4 (&raw)[8]) {
       const long kk = tile_ < tf ? tile_ : tf - 1;
-      const long tile = gtile(WPC_REVERSE ? tf - 1 - kk : kk);
+      const long tile = gtile(kk);
       const float* p = X + (tile * WG_TILE_ROWS + 8 * g) * 128 + 4 * q;
 #pragma unroll
       for (int i = 0; i < 8; ++i) raw[i] = ld4(p + i * 128);
@@ -1983,9 +1768,8 @@ __global__ void __launch_bounds__(512, 2) k_wgrad_pc(const WgradLaunch L) {
       }
       WPC_STAMP(1);
       typedef __attribute__((address_space(3))) u32x4 lds_u32x4;
-#if WPC_SPLIT_MFMA && !defined(WPC_EXP_NOSPLIT)
-      // the four features of a lane stage by stage (4 x split8_mfma interleaved: left to the compiler they run one after the
-      // other, each a chain of conversion -> MFMA -> conversion -> MFMA -> conversion that waits for the shared matrix pipe
+      // the four features of a lane stage by stage (the matrix-pipe split of wg_sel, four times, interleaved: left to the compiler
+      // they run one after the other, each a chain of conversion -> MFMA -> conversion -> MFMA -> conversion that waits for the shared matrix pipe
       // twice: 1440 cycles per tile in the s_memtime timeline)
       f32x4 r0[4], r1[4];
       u32x4 p1[4], p2[4], p3[4];
@@ -2016,37 +1800,11 @@ __global__ void __launch_bounds__(512, 2) k_wgrad_pc(const WgradLaunch L) {
         p3[e] = u32x4{pk_bf16(r0[e][0], r0[e][1]), pk_bf16(r0[e][2], r0[e][3]), pk_bf16(r1[e][0], r1[e][1]), pk_bf16(r1[e][2], r1[e][3])};
         *(lds_u32x4*)(d + 2048) = p3[e];
       }
-#else
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float v[8] = {raw[0][e], raw[1][e], raw[2][e], raw[3][e], raw[4][e], raw[5][e], raw[6][e], raw[7][e]};
-        u32x4 p1, p2, p3;
-#ifdef WPC_EXP_NOSPLIT   // timing experiment only (results are garbage): what the splits cost
-        p1 = u32x4{__builtin_bit_cast(u32, v[0]), __builtin_bit_cast(u32, v[1]), __builtin_bit_cast(u32, v[2]), __builtin_bit_cast(u32, v[3])};
-        p2 = u32x4{__builtin_bit_cast(u32, v[4]), __builtin_bit_cast(u32, v[5]), __builtin_bit_cast(u32, v[6]), __builtin_bit_cast(u32, v[7])};
-        p3 = p1 ^ p2;
-#else
-        split8(v, p1, p2, p3);
-#endif
-        lds_char* d = wa[e] + buf;
-        *(lds_u32x4*)(d) = p1;
-        *(lds_u32x4*)(d + 1024) = p2;
-        *(lds_u32x4*)(d + 2048) = p3;
-      }
-#endif
     };
     // four row sets: the loads of tile k + 3 are issued BEFORE tile k is split (they do not queue behind ~1500 cycles of splits),
     // into the set tile k - 1 left; the image index (k % 3) is a run-time offset
     int img = 0;
     auto next_img = [&]() { img = (img == (WPC_NIMG - 1) * WPC_IMG) ? 0 : img + WPC_IMG; };
-#if WPC_FLAGS
-    int kt = 0;   // local index of the tile being written
-#define WPC_P_ACQUIRE() do { if (kt >= WPC_NIMG) wpc_wait_ge(flag_done, kt - (WPC_NIMG - 1)); } while (0)
-#define WPC_P_PUBLISH() do { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); ++kt; wpc_post(flag_ready + 4 * wv, kt); } while (0)
-#else
-#define WPC_P_ACQUIRE() ((void)0)
-#define WPC_P_PUBLISH() wpc_barrier()
-#endif
     if (t0 < tf) {
       load_tile(t0, raw0);
       __builtin_amdgcn_sched_barrier(0);  // (the groups must BE issued in this order, or the loop's waits are counted for another one)
@@ -2055,40 +1813,36 @@ __global__ void __launch_bounds__(512, 2) k_wgrad_pc(const WgradLaunch L) {
       load_tile(t0 + 2, raw2);
       __builtin_amdgcn_sched_barrier(0);
       long tile = t0;
-#define WPC_STEP(cur, nxt, ahead, same)      \
+#define WPC_STEP(cur, nxt, ahead)            \
   WPC_STAMP(0);                              \
-  WPC_LOAD(tile + ahead, same, nxt);         \
+  load_tile(tile + ahead, nxt);              \
   __builtin_amdgcn_sched_barrier(0);         \
   WPC_STAMP(3);                              \
-  WPC_P_ACQUIRE();                           \
   process(cur, img);                         \
   WPC_STAMP(2);                              \
   next_img();                                \
-  WPC_P_PUBLISH()
+  wpc_barrier()
       for (; tile + 3 < tf; tile += 4) {
-        WPC_STEP(raw0, raw3, 3, t0);
-        WPC_STEP(raw1, raw0, 4, t0 + 1);
-        WPC_STEP(raw2, raw1, 5, t0 + 2);
-        WPC_STEP(raw3, raw2, 6, t0 + 3);
+        WPC_STEP(raw0, raw3, 3);
+        WPC_STEP(raw1, raw0, 4);
+        WPC_STEP(raw2, raw1, 5);
+        WPC_STEP(raw3, raw2, 6);
       }
       // (up to three tiles left; raw0..raw2 hold them: after a full round the sets are back in place)
       if (tile < tf) {
-        WPC_P_ACQUIRE();
         process(raw0, img);
         next_img();
-        WPC_P_PUBLISH();
+        wpc_barrier();
       }
       if (tile + 1 < tf) {
-        WPC_P_ACQUIRE();
         process(raw1, img);
         next_img();
-        WPC_P_PUBLISH();
+        wpc_barrier();
       }
       if (tile + 2 < tf) {
-        WPC_P_ACQUIRE();
         process(raw2, img);
         next_img();
-        WPC_P_PUBLISH();
+        wpc_barrier();
       }
     }
     if (tf < t1) {  // the ragged tile: rows past M read row M - 1; A's are zeroed
@@ -2104,9 +1858,8 @@ __global__ void __launch_bounds__(512, 2) k_wgrad_pc(const WgradLaunch L) {
         for (int i = 0; i < 8; ++i)
           if (r0 + i >= J.M) raw0[i] = f32x4{0.f, 0.f, 0.f, 0.f};
       }
-      WPC_P_ACQUIRE();
       process(raw0, img);
-      WPC_P_PUBLISH();
+      wpc_barrier();
     }
     // bias gradient: lanes (rg = 0, 1) x waves (half = 0, 1) hold partial column sums of features 4q .. 4q + 3
     wpc_barrier();  // (consumers are past their last read: the images are free)
@@ -2127,52 +1880,6 @@ __global__ void __launch_bounds__(512, 2) k_wgrad_pc(const WgradLaunch L) {
   } else {
     // ------------------------------------------------------------ consumer
     const int cw = wv - 4;
-#ifdef WPC_PRIO_C
-    __builtin_amdgcn_s_setprio(WPC_PRIO_C);
-#endif
-#if WPC_MFMA32
-    // the 64 x 64 quadrant as 2 x 2 blocks of v_mfma_f32_32x32x16_bf16 (half the matrix instructions of the 16x16x32 form for
-    // the same pipe time, and a 32-cycle instruction leaves the partner wave's vector instructions twice the room per issue):
-    // lane (i = lane & 31, hi = lane >> 5) holds feature 32 * block + i, rows 16 * s + 8 * hi .. + 7 of K-step s -- the SAME
-    // 16-byte vectors of the image, handed out to other lanes: vector (feature f, 8-row group 2 s + hi, piece p)
-    typedef float f32x16 __attribute__((ext_vector_type(16)));
-    const int li = lane & 31, hi = lane >> 5;
-    const int c = li & 15;
-    const int sl = (c ^ ((c >> 3) << 1)) ^ (li >> 4);
-    const int J0 = 64 * (cw >> 1), K0 = 64 * (cw & 1);
-    lds_char* ra = sm + ((J0 >> 4) + (li >> 4)) * 3072 + hi * 256 + 16 * sl;          // + block * 6144 + piece * 1024 + s * 512
-    lds_char* rb = sm + (8 + (K0 >> 4) + (li >> 4)) * 3072 + hi * 256 + 16 * sl;
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int jj = 0; jj < 2; ++jj)
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[jj][kk][r] = 0.f;
-    u32x4 ap[2][3][2], bp[2][3][2];
-    auto rdA = [&](int p, int img) {
-#pragma unroll
-      for (int jj = 0; jj < 2; ++jj)
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) ap[jj][p][ks] = *(lds_cu32x4*)(ra + img + jj * 6144 + p * 1024 + ks * 512);
-    };
-    auto rdB = [&](int p, int img) {
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) bp[kk][p][ks] = *(lds_cu32x4*)(rb + img + kk * 6144 + p * 1024 + ks * 512);
-    };
-    auto term = [&](int pa, int pb) {
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-        for (int jj = 0; jj < 2; ++jj)
-#pragma unroll
-          for (int kk = 0; kk < 2; ++kk)
-            acc[jj][kk] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ap[jj][pa][ks]), __builtin_bit_cast(bf16x8, bp[kk][pb][ks]),
-                                                                  acc[jj][kk], 0, 0, 0);
-    };
-#else
     const int c = lane & 15, g = lane >> 4;
     const int jb0 = 4 * (cw >> 1), kb0 = 4 * (cw & 1);
     f32x4 acc[4][4];
@@ -2199,24 +1906,15 @@ __global__ void __launch_bounds__(512, 2) k_wgrad_pc(const WgradLaunch L) {
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) acc[jj][kk] = MFMA_BF(ap[jj][pa], bp[kk][pb], acc[jj][kk]);
     };
-#endif
     const long n = t1 - t0;
-#if WPC_FLAGS
-#define WPC_C_ACQUIRE(k) wpc_wait_ge(flag_ready, (int)(k) + 1)
-#define WPC_C_RELEASE(k) wpc_post(flag_done + 4 * cw, (int)(k))
-#else
-#define WPC_C_ACQUIRE(k) wpc_barrier_c()
-#define WPC_C_RELEASE(k) ((void)0)
-#endif
     if (n > 0) {
-      WPC_C_ACQUIRE(0);   // image 0 = tile 0
+      wpc_barrier_c();   // image 0 = tile 0
       rdA(0, 0), rdB(2, 0), rdB(1, 0), rdA(1, 0), rdB(0, 0), rdA(2, 0);
       int img = 0;
       for (long k = 1; k < n; ++k) {
         img = (img == (WPC_NIMG - 1) * WPC_IMG) ? 0 : img + WPC_IMG;
         WPC_STAMP(1);
-        WPC_C_RELEASE(k - 1);   // (flags form) the images of tiles < k - 1 are free: their reads fed the MFMAs of the last iteration
-        WPC_C_ACQUIRE(k);   // image k % 3 = tile k; the registers hold tile k - 1 (the order of the accumulation does not matter
+        wpc_barrier_c();   // image k % 3 = tile k; the registers hold tile k - 1 (the order of the accumulation does not matter
                            // for accuracy here: the accumulators carry the sums of all earlier tiles)
         WPC_STAMP(0);
         // (pinned: left alone, the scheduler sinks all 24 reads below the MFMAs -- to the end of the iteration, in front of the barrier)
@@ -2225,23 +1923,17 @@ __global__ void __launch_bounds__(512, 2) k_wgrad_pc(const WgradLaunch L) {
         WPC_PIN();
         rdB(2, img);
         WPC_PIN();
-#ifndef WPC_EXP_NOMFMA
         term(0, 1);
         term(1, 1);
         WPC_PIN();
-#endif
         rdB(1, img);
         WPC_PIN();
-#ifndef WPC_EXP_NOMFMA
         term(0, 0);
         WPC_PIN();
-#endif
         rdA(0, img);
         WPC_PIN();
-#ifndef WPC_EXP_NOMFMA
         term(1, 0);
         WPC_PIN();
-#endif
         rdA(1, img);
         WPC_PIN();
         term(2, 0);
@@ -2250,29 +1942,17 @@ __global__ void __launch_bounds__(512, 2) k_wgrad_pc(const WgradLaunch L) {
         rdB(0, img);
       }
       term(0, 2);
-#ifndef WPC_EXP_NOMFMA
       term(0, 1), term(1, 1), term(0, 0), term(1, 0);
-#endif
       term(2, 0);
     }
     wpc_barrier();
     wpc_barrier();
-#if WPC_MFMA32
-    // D of the 32 x 32 form: lane (n = lane & 31, hi), register r holds row 8 * (r >> 2) + 4 * hi + (r & 3)
-#pragma unroll
-    for (int jj = 0; jj < 2; ++jj)
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) P[(J0 + 32 * jj + 8 * (r >> 2) + 4 * hi + (r & 3)) * 128 + K0 + 32 * kk + li] = acc[jj][kk][r];
-#else
 #pragma unroll
     for (int jj = 0; jj < 4; ++jj)
 #pragma unroll
       for (int kk = 0; kk < 4; ++kk)
 #pragma unroll
         for (int qq = 0; qq < 4; ++qq) P[(16 * (jb0 + jj) + 4 * g + qq) * 128 + 16 * (kb0 + kk) + c] = acc[jj][kk][qq];
-#endif
   }
   WPC_TL_DUMP();
 #ifdef MGN_TIMELINE

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """k_wgrad_x6 on the bench shape: the four E-row weight-gradient jobs of one round as ONE launch (+ k_wgrad_red), HIP-event timing.
-With MGN_LIB naming a timing-experiment build (-DWGX_EXP_NOSPLIT / -DWGX_EXP_NOMFMA: results garbage by design) it prices the parts.
+MGN_LIB names another build of the library to time instead of the shipped one.
 usage: python tools/kbench_wgrad.py [batch]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

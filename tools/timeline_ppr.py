@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Debug: s_memtime timeline of wave 0 (h = 0) and wave 4 (h = 1) of workgroup 0 of the register-resident-weights edge update
-(csrc/mgn_ppr.inc; needs tools/libexp_TLR.so = the engine built with -DMGN_TIMELINE: tools/mkvar.sh TLR -DMGN_TIMELINE).
+(csrc/mgn_ppr.inc; needs tools/libexp_TLR.so = the engine built with -DMGN_TIMELINE).
 Per half, mean shader cycles of the eight intervals of a group: wait at the barrier that opens the first unit, the first
 unit's matrix phase (+ its closing wait / row sums), wait at the mid barrier, the boundary phase, and the same for the second unit.
 usage: python tools/timeline_ppr.py [save]"""

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Round-5 evidence for k_wgrad_pc in ONE GPU call (variant builds tools/libexp_<TAG>.so must exist: tools/mkvar.sh):
+# Round-5 evidence for k_wgrad_pc in ONE GPU call (needs the -DMGN_TIMELINE build tools/libexp_TLW.so; the timing-only variant builds of round 5 are run only where their tools/libexp_<TAG>.so still exists: their switches left csrc/):
 #   gpurun_out/r05_wgrad_experiments.txt  A/B against k_wgrad_x6 and the timing-only / alternative builds
 #   gpurun_out/r05_wgrad_timeline.txt     s_memtime timelines, single launch and the last of 100 back-to-back launches
 #   gpurun_out/r05_wgrad_pmc.csv          SQ counters of the kernel (tools/pmc_wgrad.sh)

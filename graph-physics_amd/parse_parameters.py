@@ -13,6 +13,45 @@ from .processors import EncodeProcessDecode
 from .simulator import Simulator
 
 
+def get_preprocessing(param: Dict[str, Any], device: torch.device, use_edge_feature: bool = True, remove_noise: bool = False,
+                      extra_node_features=None, extra_edge_features=None):
+    """The preprocessing callable of a config (training/parse_parameters.py:24-78): reads
+    ``transformations.preprocessing.noise`` / ``noise_index_start`` / ``noise_index_end``,
+    ``transformations.world_pos_parameters`` and ``index.node_type_index`` and returns
+    ``preprocess.build_preprocessing(...)``, a callable ``f(graph, step=0)`` over tensors on ``device`` (constructing it
+    needs no GPU).
+
+    The one place where the split differs from the reference: the reference honours ``dataset.khop`` in its Dataset class
+    (training/parse_parameters.py:224, dataset/dataset.py:206-242); the engine has no Dataset class, so the key is read
+    here and the k-hop expansion becomes the last step of the callable, with a per-trajectory cache keyed by
+    ``graph.traj_index``.  ``dataset.khop`` defaults to 1; a non-integer or a value below 1 is a ``ValueError``.
+    ``dataset.new_edges_ratio > 0`` (random extra edges) is not implemented and raises rather than train on another graph."""
+    from .preprocess import build_preprocessing
+
+    prep = param.get("transformations", {}).get("preprocessing", {})
+    noise_scale = prep.get("noise", 0)
+    noise_parameters = None
+    if noise_scale != 0 and not remove_noise:
+        noise_parameters = {"noise_index_start": prep.get("noise_index_start"), "noise_index_end": prep.get("noise_index_end"),
+                            "noise_scale": noise_scale, "node_type_index": param["index"]["node_type_index"]}
+    world = param.get("transformations", {}).get("world_pos_parameters", {})
+    world_pos_parameters = None
+    if world.get("use", False):
+        world_pos_parameters = {"world_pos_index_start": world.get("world_pos_index_start"),
+                                "world_pos_index_end": world.get("world_pos_index_end"),
+                                "node_type_index": param["index"]["node_type_index"]}
+    dataset = param.get("dataset", {})
+    khop = dataset.get("khop", 1)
+    if isinstance(khop, bool) or not isinstance(khop, int) or khop < 1:
+        raise ValueError(f"dataset.khop: an integer >= 1, got {khop!r}")
+    ratio = dataset.get("new_edges_ratio", 0)
+    if ratio is not None and ratio > 0:
+        raise NotImplementedError("dataset.new_edges_ratio: random extra edges are not implemented by this engine")
+    return build_preprocessing(noise_parameters=noise_parameters, world_pos_parameters=world_pos_parameters,
+                               add_edges_features=use_edge_feature, extra_node_features=extra_node_features,
+                               extra_edge_features=extra_edge_features, khop=khop, khop_cache={} if khop > 1 else None)
+
+
 def get_model(param: Dict[str, Any], only_processor: bool = False):
     model = param.get("model", {})
     model_type = model.get("type", "")

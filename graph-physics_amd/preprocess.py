@@ -85,6 +85,61 @@ def add_world_edges(x: torch.Tensor, edge_index: torch.Tensor, world_pos_index_s
     return out[:, :int(n.item())].contiguous()
 
 
+def _khop(edge_index: torch.Tensor, num_nodes: int, num_hops: int):
+    """(k-hop edge_index, number of rows that took the bitmap path of csrc/mgn_khop.hip)"""
+    import ctypes as C
+
+    L = _capi.lib()
+    dev = edge_index.device
+    if edge_index.dim() != 2 or edge_index.shape[0] != 2:
+        raise ValueError("edge_index must have shape [2, E]")
+    ei = edge_index.to(torch.int64).contiguous()
+    N, E = int(num_nodes), int(ei.shape[1])
+    nbytes = L.mgn_khop_workspace_bytes(N, E)
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    n_out, n_ovf = C.c_int64(0), C.c_int64(0)
+    with torch.cuda.device(dev):
+        rc = L.mgn_khop_count(ei[0].data_ptr(), ei[1].data_ptr(), E, N, int(num_hops), C.byref(n_out), C.byref(n_ovf),
+                              _ptr(ws), nbytes, _stream(dev))
+        if rc == 3:
+            raise IndexError(f"edge_index has entries outside [0, {N})")
+        _capi.check(rc, "mgn_khop_count", khop=True)
+        out = torch.empty(2, n_out.value, dtype=torch.int64, device=dev)
+        if n_out.value > 0:
+            rc = L.mgn_khop_fill(_ptr(ws), nbytes, N, int(num_hops), out[0].data_ptr(), out[1].data_ptr(), n_out.value, _stream(dev))
+            _capi.check(rc, "mgn_khop_fill", khop=True)
+    return out, n_ovf.value
+
+
+def khop_edges(edge_index: torch.Tensor, num_nodes: int, num_hops: int) -> torch.Tensor:
+    """``compute_k_hop_edge_index`` of the reference (utils/torch_graph.py:14-105) on the device: the int64 [2, E_k] set of
+    ordered pairs (i, j), i != j, such that a directed walk of 1..``num_hops`` edges leads from i (row 0) to j (row 1),
+    sorted by (row 0, row 1), each pair once -- the order of the coalesced COO tensor the reference returns.  The input may be
+    unsorted, hold duplicates and self loops, be asymmetric and leave nodes isolated.  ``num_hops == 1`` returns the input
+    object unchanged (the reference expands only for ``khop > 1``); ``num_hops < 1`` is a ``ValueError``.
+
+    One wavefront searches one row in LDS; a row with more than ``mgn_khop_row_capacity()`` (1024) entries -- a hub node, a
+    large k on a 3-D mesh -- goes through a bitmap search in global memory that is exact but slow (about 3 * N/32 words per
+    level per such row).  One-time topology prep: synchronises to read E_k."""
+    if isinstance(num_hops, bool) or not isinstance(num_hops, int):
+        raise ValueError(f"num_hops must be an integer >= 1, got {num_hops!r}")
+    if num_hops < 1:
+        raise ValueError(f"num_hops must be >= 1, got {num_hops}")
+    _require_device(edge_index)
+    if num_hops == 1:
+        return edge_index
+    return _khop(edge_index, num_nodes, num_hops)[0]
+
+
+def khop_graph(graph, num_hops: int, add_edge_features: bool = True):
+    """``compute_k_hop_graph`` of the reference (utils/torch_graph.py): ``graph.edge_index`` becomes its k-hop expansion;
+    with ``add_edge_features`` ``graph.edge_attr`` is recomputed on the new edges as mesh-space Cartesian + Distance only
+    (earlier extra edge columns are dropped, as the reference does), otherwise it is removed (``_may_remove_edges_attr``)."""
+    graph.edge_index = khop_edges(graph.edge_index, int(graph.x.shape[0] if graph.x is not None else graph.pos.shape[0]), num_hops)
+    graph.edge_attr = edge_features(graph.pos, graph.edge_index) if add_edge_features else None
+    return graph
+
+
 def add_noise(graph, noise_index_start, noise_index_end, noise_scale, node_type_index: int, t: Optional[float] = None,
               seed: int = 0, offset: int = 0):
     """``add_noise`` of the reference (preprocessing.py:177-238), on the device and in place: Gaussian noise
@@ -147,12 +202,22 @@ def add_world_pos_features(graph, world_pos_index_start: int, world_pos_index_en
 
 
 def build_preprocessing(noise_parameters=None, world_pos_parameters=None, add_edges_features: bool = True,
-                        extra_node_features=None, extra_edge_features=None, seed: int = 0):
+                        extra_node_features=None, extra_edge_features=None, seed: int = 0, khop: int = 1,
+                        khop_cache: Optional[dict] = None):
     """Device-side ``build_preprocessing`` (preprocessing.py:380-444): the same transform ORDER as the
     reference -- extra node features, [obstacle next pos,] faces -> edges, [world edges,] edge features,
     noise inserted at position 1, extra edge features -- as one callable
     ``f(graph, step=0) -> graph`` over device tensors (``graph.face`` [K,F], ``graph.pos``, ``graph.x``,
-    ``graph.y``).  Topology-only results (edge_index) can be cached by the caller across a trajectory."""
+    ``graph.y``).  Topology-only results (edge_index) can be cached by the caller across a trajectory.
+
+    ``khop > 1`` appends the k-hop expansion (``khop_graph``) as the LAST step: the reference applies it after the whole
+    preprocessing callable (dataset/h5_dataset.py:184-185).  With a dict as ``khop_cache`` and a graph that carries
+    ``traj_index``, the k-hop ``edge_index`` (and, with edge features, ``edge_attr``) is kept per trajectory as device tensors
+    and reused, as dataset/dataset.py:216-241 does on the host.  This mirrors a quirk of the reference: the cached
+    ``edge_attr`` is that of the FIRST frame seen of a trajectory, also where later frames move the mesh.  ``khop == 1``
+    leaves the callable as it is without the argument."""
+    if isinstance(khop, bool) or not isinstance(khop, int) or khop < 1:
+        raise ValueError(f"khop must be an integer >= 1, got {khop!r}")
     steps = []
     if extra_node_features is not None:
         steps += list(extra_node_features) if isinstance(extra_node_features, (list, tuple)) else [extra_node_features]
@@ -187,6 +252,21 @@ def build_preprocessing(noise_parameters=None, world_pos_parameters=None, add_ed
                                                   seed=seed, offset=step))
     if extra_edge_features is not None:
         steps += list(extra_edge_features) if isinstance(extra_edge_features, (list, tuple)) else [extra_edge_features]
+    if khop > 1:
+        def k_hop(g, step):
+            traj = g.traj_index if khop_cache is not None else None
+            if traj is not None:
+                traj = int(traj)
+                if traj in khop_cache:
+                    g.edge_index, attr = khop_cache[traj]
+                    if add_edges_features:
+                        g.edge_attr = attr
+                    return g
+            g = khop_graph(g, khop, add_edge_features=add_edges_features)
+            if traj is not None:
+                khop_cache[traj] = (g.edge_index, g.edge_attr)
+            return g
+        steps.append(k_hop)
 
     def run(graph, step: int = 0):
         import inspect

@@ -747,6 +747,33 @@ int mgn_loss_fwd(const mgn_loss_args* args, void* stream);
 int mgn_loss_bwd(const mgn_loss_args* args, const float* g, float* d_net, float* d_u, float* dge, void* stream);
 const char* mgn_loss_last_error(void);
 
+/* ================================================================================
+ * k-hop edge sets (the config key dataset.khop) -- csrc/mgn_khop.hip
+ * ================================================================================
+ * compute_k_hop_edge_index of the reference (graphphysics/utils/torch_graph.py:14-105, applied per trajectory on the CPU by
+ * dataset/dataset.py:206-242): the set of ordered pairs (i, j), i != j, such that a directed walk of 1..hops edges of the
+ * input graph leads from i (row0) to j (row1); sorted by (row0, row1), each pair once -- the order of a coalesced COO
+ * tensor.  The input may be unsorted, hold duplicates and self loops, be asymmetric and leave nodes isolated.
+ * The output size is not known in advance, so the call is split in two; everything the second half needs from the first
+ * lives in the caller's workspace (no hidden state):
+ *   mgn_khop_count  coalesces the input into a CSR (key / radix sort / unique as mgn_faces_to_edges), sizes every row
+ *                   (one wavefront per row: hash set + queue in LDS; rows above mgn_khop_row_capacity() ids go through a
+ *                   bitmap search in the workspace, exact but slow: ~3 * N/32 words per level per such row), scans the
+ *                   sizes and returns the number of pairs in *n_out_host and the number of rows that took the bitmap path
+ *                   in *n_overflow_rows_host (both HOST pointers).  Synchronises `stream`: topology preparation like
+ *                   mgn_faces_to_edges, not capturable.  Returns 3 on an index outside [0, N).
+ *   mgn_khop_fill   writes the pairs into out0 / out1 (int64, capacity `cap` >= the counted number, else 1 before any
+ *                   launch).  Reads the header mgn_khop_count left in `ws` (one small copy to the host) and uses the
+ *                   workspace's bitmap region as scratch.  No global atomics: bit-identical from run to run.
+ * 1 <= N <= 2^31 - 2 (node ids are 32-bit on chip, all-ones marks an empty slot), hops >= 2, E >= 0; anything else, or a
+ * workspace below mgn_khop_workspace_bytes(N, E), returns 1 before any launch.  2 = HIP error.  mgn_khop_last_error(). */
+size_t mgn_khop_workspace_bytes(int64_t N, int64_t E);
+int mgn_khop_row_capacity(void);
+int mgn_khop_count(const int64_t* row0, const int64_t* row1, int64_t E, int64_t N, int hops, int64_t* n_out_host,
+                   int64_t* n_overflow_rows_host, void* ws, size_t ws_bytes, void* stream);
+int mgn_khop_fill(const void* ws, size_t ws_bytes, int64_t N, int hops, int64_t* out0, int64_t* out1, int64_t cap, void* stream);
+const char* mgn_khop_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,7 +15,8 @@ _CSRC = os.path.join(_HERE, "csrc")
 _REPO = os.path.dirname(_HERE)
 LIB_PATH = os.environ.get("MGN_LIB") or os.path.join(_CSRC, "libmgn_hip.so")
 SOURCES = [os.path.join(_CSRC, "mgn_kernels.hip"), os.path.join(_CSRC, "mgn_prep.hip"), os.path.join(_CSRC, "mgn_attn.hip"),
-           os.path.join(_CSRC, "mgn_dense.hip"), os.path.join(_CSRC, "mgn_loss.hip"), os.path.join(_CSRC, "mgn_khop.hip")]
+           os.path.join(_CSRC, "mgn_dense.hip"), os.path.join(_CSRC, "mgn_loss.hip"), os.path.join(_CSRC, "mgn_khop.hip"),
+           os.path.join(_CSRC, "mgn_subgraph.hip")]
 DEPS = [os.path.join(_CSRC, "mgn_x6.inc"), os.path.join(_CSRC, "mgn_fused.inc"), os.path.join(_CSRC, "mgn_pp.inc"), os.path.join(_CSRC, "mgn_ppr.inc")]  # included by the source
 HEADER = os.path.join(_REPO, "include", "mgn_hip.h")
 # No packed-fp32 VALU (v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32) in device code: beside a SIMD partner that streams MFMAs
@@ -191,6 +192,15 @@ class LossArgs(C.Structure):
     ]
 
 
+MAX_GATHER_JOBS = 8
+
+
+class GatherJob(C.Structure):
+    """mgn_gather_job (include/mgn_hip.h)"""
+    _fields_ = [("src", _f32p), ("ld_src", C.c_int64), ("width", C.c_int64), ("idx", C.c_void_p), ("rows", C.c_int64), ("dst", _f32p),
+                ("ld_dst", C.c_int64), ("src_rows", C.c_int64)]
+
+
 #: every symbol include/mgn_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "mgn_version": (C.c_int, []),
@@ -286,6 +296,13 @@ SYMBOLS = {
                                  C.c_void_p, C.c_size_t, C.c_void_p]),
     "mgn_khop_fill": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "mgn_khop_last_error": (C.c_char_p, []),
+    "mgn_subgraph_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "mgn_subgraph_block_edges": (C.c_int, []),
+    "mgn_subgraph_count": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p,
+                                     C.c_size_t, C.c_void_p]),
+    "mgn_subgraph_fill": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "mgn_gather_rows_batch": (C.c_int, [C.c_int, C.POINTER(GatherJob), C.c_void_p]),
+    "mgn_subgraph_last_error": (C.c_char_p, []),
 }
 
 _lib = None
@@ -398,8 +415,9 @@ def lib():
     return _lib
 
 
-def check(rc: int, what: str, prep: bool = False, attn: bool = False, dense: bool = False, loss: bool = False, khop: bool = False):
+def check(rc: int, what: str, prep: bool = False, attn: bool = False, dense: bool = False, loss: bool = False, khop: bool = False,
+          subgraph: bool = False):
     if rc != 0:
-        fn = lib().mgn_khop_last_error if khop else lib().mgn_loss_last_error if loss else lib().mgn_dense_last_error if dense else (lib().mgn_attn_last_error if attn else (lib().mgn_prep_last_error if prep else lib().mgn_last_error))
+        fn = lib().mgn_subgraph_last_error if subgraph else lib().mgn_khop_last_error if khop else lib().mgn_loss_last_error if loss else lib().mgn_dense_last_error if dense else (lib().mgn_attn_last_error if attn else (lib().mgn_prep_last_error if prep else lib().mgn_last_error))
         msg = fn().decode("utf-8", "replace")
         raise RuntimeError(f"{what} failed (code {rc}): {msg}")

@@ -14,7 +14,8 @@ from .simulator import Simulator
 
 
 def get_preprocessing(param: Dict[str, Any], device: torch.device, use_edge_feature: bool = True, remove_noise: bool = False,
-                      extra_node_features=None, extra_edge_features=None):
+                      extra_node_features=None, extra_edge_features=None, use_partitioning: bool = False,
+                      num_partitions: Optional[int] = None, max_nodes_per_partition: Optional[int] = None):
     """The preprocessing callable of a config (training/parse_parameters.py:24-78): reads
     ``transformations.preprocessing.noise`` / ``noise_index_start`` / ``noise_index_end``,
     ``transformations.world_pos_parameters`` and ``index.node_type_index`` and returns
@@ -25,7 +26,14 @@ def get_preprocessing(param: Dict[str, Any], device: torch.device, use_edge_feat
     (training/parse_parameters.py:224, dataset/dataset.py:206-242); the engine has no Dataset class, so the key is read
     here and the k-hop expansion becomes the last step of the callable, with a per-trajectory cache keyed by
     ``graph.traj_index``.  ``dataset.khop`` defaults to 1; a non-integer or a value below 1 is a ``ValueError``.
-    ``dataset.new_edges_ratio > 0`` (random extra edges) is not implemented and raises rather than train on another graph."""
+    ``dataset.new_edges_ratio > 0`` (random extra edges) is not implemented and raises rather than train on another graph.
+
+    ``use_partitioning`` with ``num_partitions`` or ``max_nodes_per_partition`` are the reference's ``get_dataset`` arguments
+    of the same names (train.py ``--use_partitioning --num_partitions / --max_nodes_per_partition``): every sample becomes one
+    part of the mesh, cut as the last step (``preprocess.build_preprocessing(partitioning=...)``), and the callable takes a
+    keyword ``part``.  Naming both counts or neither is the reference's ``ValueError``.  A part carries no ``face``: a config
+    whose loss section needs it (physics terms with ``gradient_method: least_squares``) is refused here with a ``ValueError``,
+    not by the first training step.  Without ``use_partitioning`` the two counts are ignored, as in the reference."""
     from .preprocess import build_preprocessing
 
     prep = param.get("transformations", {}).get("preprocessing", {})
@@ -47,9 +55,26 @@ def get_preprocessing(param: Dict[str, Any], device: torch.device, use_edge_feat
     ratio = dataset.get("new_edges_ratio", 0)
     if ratio is not None and ratio > 0:
         raise NotImplementedError("dataset.new_edges_ratio: random extra edges are not implemented by this engine")
+    extra = {}
+    if use_partitioning:
+        from .preprocess import num_partitions_for
+
+        num_partitions_for(1, num_partitions, max_nodes_per_partition)   # both / neither: the reference's errors
+        check_partitioned_loss(param)
+        extra["partitioning"] = {"num_partitions": num_partitions, "max_nodes_per_partition": max_nodes_per_partition}
     return build_preprocessing(noise_parameters=noise_parameters, world_pos_parameters=world_pos_parameters,
                                add_edges_features=use_edge_feature, extra_node_features=extra_node_features,
-                               extra_edge_features=extra_edge_features, khop=khop, khop_cache={} if khop > 1 else None)
+                               extra_edge_features=extra_edge_features, khop=khop, khop_cache={} if khop > 1 else None, **extra)
+
+
+def check_partitioned_loss(param: Dict[str, Any], loss=None) -> None:
+    """``ValueError`` when the loss of the config (or ``loss``, a loss object, with the config's ``loss.gradient_method``)
+    reads ``graph.face``: the parts of a partitioned mesh carry none (``preprocess.apply_partition``, as upstream)."""
+    if loss is None:
+        loss = get_loss(param)[0]
+    if isinstance(loss, MultiLoss) and loss.needs_physical_fields and get_gradient_method(param) == "least_squares":
+        raise ValueError("use_partitioning: the physics losses with gradient_method 'least_squares' need graph.face, which the parts "
+                         "of a partitioned mesh do not carry (cut edges and faces are dropped); use 'finite_diff' or train unpartitioned")
 
 
 def get_model(param: Dict[str, Any], only_processor: bool = False):

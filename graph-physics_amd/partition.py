@@ -6,7 +6,9 @@ approximation; here the partitioned forward/backward is EXACTLY the single-devic
 one: every directed edge lives on the rank that owns its destination, so the
 aggregation is local, edge latents never move, and the only remote data a round
 needs are the (projected) latent rows of ghost SOURCE nodes -- one neighbour
-exchange per round.
+exchange per round.  (The reference's own scheme -- one part per sample on ONE device,
+cut edges dropped -- is ``preprocess.apply_partition`` / ``build_preprocessing(partitioning=...)``
+and takes its node sets from ``partition_nodes`` below.)
 
 Partitioner.  The reference reaches METIS through PyG ``ClusterData``
 (torch_graph.py:127-135); no METIS library exists in this image, so the same

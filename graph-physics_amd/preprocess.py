@@ -140,6 +140,205 @@ def khop_graph(graph, num_hops: int, add_edge_features: bool = True):
     return graph
 
 
+# ----------------------------------------------------------------------------------------- induced sub-meshes (partitioning)
+def _rows_as_words(t: torch.Tensor) -> torch.Tensor:
+    """a [R, W] view of ``t`` in 32-bit elements (what mgn_gather_rows_batch copies)"""
+    if t.dim() == 1:
+        t = t.unsqueeze(1)
+    if t.dim() != 2:
+        t = t.reshape(t.shape[0], -1)
+    if t.element_size() % 4 != 0:
+        raise ValueError(f"row gather: rows of {t.dtype} are not made of 32-bit elements")
+    if t.stride(-1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        t = t.contiguous()
+    return t if t.dtype == torch.float32 else t.view(torch.int32)
+
+
+def gather_rows_batch(sources, indices):
+    """``[src[idx] for src, idx in zip(sources, indices)]`` as ONE launch of ``mgn_gather_rows_batch`` (up to 8 tensors; a
+    ``None`` source gives ``None``).  Rows of any width made of 32-bit elements, int64 indices; no host synchronisation."""
+    live = [(i, s) for i, s in enumerate(sources) if s is not None]
+    if len(live) > _capi.MAX_GATHER_JOBS:
+        raise ValueError(f"at most {_capi.MAX_GATHER_JOBS} tensors per launch")
+    outs = [None] * len(sources)
+    if not live:
+        return outs
+    _require_device(*[s for _, s in live], *[indices[i] for i, _ in live])
+    dev = live[0][1].device
+    jobs = (_capi.GatherJob * len(live))()
+    keep = []
+    n = 0
+    for i, s in live:
+        idx = indices[i]
+        if idx.dtype != torch.int64 or not idx.is_contiguous():
+            idx = idx.to(torch.int64).contiguous()
+        rows = int(idx.numel())
+        out = torch.empty((rows,) + tuple(s.shape[1:]), dtype=s.dtype, device=dev)
+        outs[i] = out
+        if rows == 0 or out.numel() == 0:
+            continue
+        w_src, w_dst = _rows_as_words(s), _rows_as_words(out)
+        j = jobs[n]
+        j.src, j.ld_src, j.width, j.idx, j.rows = w_src.data_ptr(), int(w_src.stride(0)) if w_src.shape[0] > 1 else int(w_src.shape[1]), int(w_src.shape[1]), idx.data_ptr(), rows
+        j.dst, j.ld_dst, j.src_rows = w_dst.data_ptr(), int(w_dst.shape[1]), int(w_src.shape[0])
+        keep += [w_src, w_dst, idx]
+        n += 1
+    if n:
+        with torch.cuda.device(dev):
+            rc = _capi.lib().mgn_gather_rows_batch(n, jobs, _stream(dev))
+        _capi.check(rc, "mgn_gather_rows_batch", subgraph=True)
+    return outs
+
+
+def _subgraph_count(subset: torch.Tensor, ei: torch.Tensor, N: int, ws: torch.Tensor) -> int:
+    """``mgn_subgraph_count``: the one call of the sub-mesh path that synchronises with the host (tests count its calls)"""
+    import ctypes as C
+
+    dev = ei.device
+    S, E = int(subset.numel()), int(ei.shape[1])
+    n_edges = C.c_int64(0)
+    with torch.cuda.device(dev):
+        rc = _capi.lib().mgn_subgraph_count(subset.data_ptr() if S else None, S, N, ei[0].data_ptr() if E else None,
+                                            ei[1].data_ptr() if E else None, E, C.byref(n_edges), _ptr(ws), ws.numel(), _stream(dev))
+    if rc == 3:
+        raise IndexError(f"subset or edge_index has entries outside [0, {N})")
+    if rc == 5:
+        raise ValueError("subset lists a node twice")
+    _capi.check(rc, "mgn_subgraph_count", subgraph=True)
+    return n_edges.value
+
+
+def _subgraph_edges(subset: torch.Tensor, edge_index: torch.Tensor, num_nodes: int, want_mask: bool = False):
+    """(edge_index' int64 [2, E'], edge_pos int64 [E'], edge mask bool [E] or None) of csrc/mgn_subgraph.hip"""
+    L = _capi.lib()
+    dev = edge_index.device
+    if edge_index.dim() != 2 or edge_index.shape[0] != 2:
+        raise ValueError("edge_index must have shape [2, E]")
+    if subset.dim() != 1 or subset.dtype == torch.bool or subset.is_floating_point():
+        raise ValueError("subset must be a 1-D tensor of node indices")
+    ei = edge_index if edge_index.dtype == torch.int64 and edge_index.is_contiguous() else edge_index.to(torch.int64).contiguous()
+    ids = subset if subset.dtype == torch.int64 and subset.is_contiguous() else subset.to(torch.int64).contiguous()
+    N, E = int(num_nodes), int(ei.shape[1])
+    nbytes = L.mgn_subgraph_workspace_bytes(N, E)
+    if nbytes == 0:
+        raise ValueError(f"subgraph: num_nodes = {N} / {E} edges are outside what the kernels index")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    n = _subgraph_count(ids, ei, N, ws)
+    out = torch.empty(2, n, dtype=torch.int64, device=dev)
+    edge_pos = torch.empty(n, dtype=torch.int64, device=dev)
+    mask = torch.empty(E, dtype=torch.uint8, device=dev) if want_mask else None
+    with torch.cuda.device(dev):
+        rc = L.mgn_subgraph_fill(_ptr(ws), nbytes, E, out[0].data_ptr() if n else None, out[1].data_ptr() if n else None,
+                                 edge_pos.data_ptr() if n else None, mask.data_ptr() if want_mask and E else None, n, _stream(dev))
+    _capi.check(rc, "mgn_subgraph_fill", subgraph=True)
+    return out, edge_pos, (mask.view(torch.bool) if want_mask else None)
+
+
+def subgraph(subset: torch.Tensor, edge_index: torch.Tensor, edge_attr: Optional[torch.Tensor] = None,
+             num_nodes: Optional[int] = None, return_edge_mask: bool = False):
+    """``torch_geometric.utils.subgraph(subset, edge_index, edge_attr, relabel_nodes=True, num_nodes=...)`` of torch-geometric
+    2.6.1 for an INDEX subset, on the device: the edges with both ends in ``subset`` in input order, relabelled to the position
+    in ``subset`` (which need not be sorted), their ``edge_attr`` rows; duplicates and self loops of the input are kept.  Returns
+    ``(edge_index' int64 [2, E'], edge_attr' or None)`` and with ``return_edge_mask`` also the bool ``[E]`` mask of kept edges.
+    ``num_nodes`` defaults to ``edge_index.max() + 1`` as in PyG (one more host synchronisation).  An entry of ``subset`` or
+    ``edge_index`` outside ``[0, num_nodes)`` is an ``IndexError``, a node listed twice a ``ValueError`` (PyG relabels such a
+    subset to whichever position was scattered last).  Synchronises once to read E'."""
+    _require_device(subset, edge_index, edge_attr)
+    if num_nodes is None:
+        num_nodes = int(edge_index.max()) + 1 if edge_index.numel() else 0
+    out, edge_pos, mask = _subgraph_edges(subset, edge_index, num_nodes, want_mask=return_edge_mask)
+    attr = gather_rows_batch([edge_attr], [edge_pos])[0]
+    return (out, attr, mask) if return_edge_mask else (out, attr)
+
+
+class PartitionPlan:
+    """What every frame of one (trajectory, part) shares: the part's sorted node ids, its relabelled ``edge_index`` and the
+    position of each of its edges in the full mesh's edge list."""
+
+    def __init__(self, node_ids: torch.Tensor, edge_index: torch.Tensor, edge_pos: torch.Tensor):
+        self.node_ids, self.edge_index, self.edge_pos = node_ids, edge_index, edge_pos
+
+
+def _graph_num_nodes(graph) -> int:
+    if graph.num_nodes is not None:
+        return int(graph.num_nodes)
+    return int(graph.x.shape[0] if graph.x is not None else graph.pos.shape[0])
+
+
+def partition_plan(graph, node_ids: torch.Tensor) -> PartitionPlan:
+    """The topology half of ``apply_partition``: sort ``node_ids``, cut ``graph.edge_index`` (``mgn_subgraph_count`` +
+    ``mgn_subgraph_fill``; synchronises once).  Valid for every frame of the trajectory whose ``edge_index`` is the same."""
+    _require_device(node_ids, graph.edge_index)
+    ids = torch.sort(node_ids.to(torch.int64))[0]
+    ei, edge_pos, _ = _subgraph_edges(ids, graph.edge_index, _graph_num_nodes(graph))
+    return PartitionPlan(ids, ei, edge_pos)
+
+
+def apply_partition(graph, node_ids: Optional[torch.Tensor], plan: Optional[PartitionPlan] = None):
+    """``BaseDataset._apply_partition`` of the reference (dataset/dataset.py:244-302): the induced sub-mesh of the sorted
+    ``node_ids`` as a NEW ``Graph`` with ``x``, ``y``, ``pos`` (rows of the part's nodes), ``edge_index`` (relabelled),
+    ``edge_attr`` (rows of the kept edges), ``num_nodes`` and ``traj_index``.  Nothing else is carried over: ``face`` is
+    dropped, as in the reference, and edges that leave the part are dropped -- an approximation of the full-mesh step.
+    With the ``plan`` of an earlier call for this part (``partition_plan``) the call is one ``mgn_gather_rows_batch`` launch
+    and does not synchronise with the host; ``node_ids`` is then not looked at."""
+    from .mesh import Graph
+
+    if plan is None:
+        plan = partition_plan(graph, node_ids)
+    ids, pos_e = plan.node_ids, plan.edge_pos
+    x, y, pos, attr = gather_rows_batch([graph.x, graph.y, graph.pos, graph.edge_attr], [ids, ids, ids, pos_e])
+    return Graph(x=x, y=y, pos=pos, edge_index=plan.edge_index, edge_attr=attr, num_nodes=int(ids.numel()),
+                 traj_index=graph.traj_index)
+
+
+def num_partitions_for(num_nodes: int, num_partitions: Optional[int] = None, max_nodes_per_partition: Optional[int] = None) -> int:
+    """The number of parts of a trajectory with ``num_nodes`` nodes (``BaseDataset.__init__`` and ``_add_traj_to_index_map``,
+    dataset/dataset.py:72-80,135-139): ``num_partitions`` as given, or ``ceil(num_nodes / max_nodes_per_partition)``; naming
+    both or neither is a ``ValueError``."""
+    import math
+
+    if num_partitions is not None and max_nodes_per_partition is not None:
+        raise ValueError("Specify either 'num_partitions' or 'max_nodes_per_partition', not both.")
+    if num_partitions is None and max_nodes_per_partition is None:
+        raise ValueError("If 'use_partitioning' is True, specify either 'num_partitions' or 'max_nodes_per_partition'.")
+    if num_partitions is not None:
+        if isinstance(num_partitions, bool) or not isinstance(num_partitions, int) or num_partitions < 1:
+            raise ValueError(f"num_partitions must be an integer >= 1, got {num_partitions!r}")
+        return num_partitions
+    if isinstance(max_nodes_per_partition, bool) or not isinstance(max_nodes_per_partition, int) or max_nodes_per_partition < 1:
+        raise ValueError(f"max_nodes_per_partition must be an integer >= 1, got {max_nodes_per_partition!r}")
+    return max(1, math.ceil(int(num_nodes) / max_nodes_per_partition))
+
+
+def partition_sample(local_index: int, num_partitions: int):
+    """``(frame_in_traj, part)`` of sample ``local_index`` of a trajectory cut into ``num_partitions`` parts
+    (``BaseDataset._get_indices``, dataset/dataset.py:122-123): the parts of one frame are consecutive samples."""
+    return int(local_index) // int(num_partitions), int(local_index) % int(num_partitions)
+
+
+def partition_node_ids(graph, num_partitions: int, method: str = "auto", seed: int = 0):
+    """The node ids of each of the ``num_partitions`` parts of ``graph`` as a list of sorted int64 tensors on the graph's
+    device (``create_subgraphs`` of the reference, utils/torch_graph.py:108-135).  The parts are those of THIS project's
+    partitioner (``partition.partition_nodes``: coordinate bisection + boundary refinement where ``graph.pos`` exists, the
+    multilevel scheme otherwise), not METIS' -- the reference reaches METIS through PyG ``ClusterData``, and no two
+    partitioners cut a mesh alike.  Host side, once per trajectory.  ``num_partitions == 1`` gives ``[arange(N)]``."""
+    import numpy as np
+
+    from .partition import partition_nodes
+
+    if isinstance(num_partitions, bool) or not isinstance(num_partitions, int) or num_partitions < 1:
+        raise ValueError(f"num_partitions must be an integer >= 1, got {num_partitions!r}")
+    N = _graph_num_nodes(graph)
+    dev = graph.edge_index.device
+    if num_partitions == 1:
+        return [torch.arange(N, dtype=torch.int64, device=dev)]
+    pos = graph.pos.detach().cpu().numpy() if graph.pos is not None else None
+    part = np.asarray(partition_nodes(pos, graph.edge_index, num_partitions, method=method, seed=seed))
+    if part.shape[0] < N:   # without coordinates the partitioner sizes the graph by its largest edge entry
+        part = np.concatenate([part, np.zeros(N - part.shape[0], dtype=part.dtype)])
+    return [torch.from_numpy(np.nonzero(part == p)[0].astype(np.int64)).to(dev) for p in range(num_partitions)]
+
+
 def add_noise(graph, noise_index_start, noise_index_end, noise_scale, node_type_index: int, t: Optional[float] = None,
               seed: int = 0, offset: int = 0):
     """``add_noise`` of the reference (preprocessing.py:177-238), on the device and in place: Gaussian noise
@@ -203,7 +402,7 @@ def add_world_pos_features(graph, world_pos_index_start: int, world_pos_index_en
 
 def build_preprocessing(noise_parameters=None, world_pos_parameters=None, add_edges_features: bool = True,
                         extra_node_features=None, extra_edge_features=None, seed: int = 0, khop: int = 1,
-                        khop_cache: Optional[dict] = None):
+                        khop_cache: Optional[dict] = None, partitioning: Optional[dict] = None):
     """Device-side ``build_preprocessing`` (preprocessing.py:380-444): the same transform ORDER as the
     reference -- extra node features, [obstacle next pos,] faces -> edges, [world edges,] edge features,
     noise inserted at position 1, extra edge features -- as one callable
@@ -215,7 +414,21 @@ def build_preprocessing(noise_parameters=None, world_pos_parameters=None, add_ed
     ``traj_index``, the k-hop ``edge_index`` (and, with edge features, ``edge_attr``) is kept per trajectory as device tensors
     and reused, as dataset/dataset.py:216-241 does on the host.  This mirrors a quirk of the reference: the cached
     ``edge_attr`` is that of the FIRST frame seen of a trajectory, also where later frames move the mesh.  ``khop == 1``
-    leaves the callable as it is without the argument."""
+    leaves the callable as it is without the argument.
+
+    ``partitioning`` (a dict with ``num_partitions`` or ``max_nodes_per_partition``, optionally ``method`` / ``seed`` for
+    ``partition_node_ids``) makes every sample ONE part of the mesh (``apply_partition``), as ``--use_partitioning`` does in
+    the reference: the callable becomes ``f(graph, step=0, part=None)``, ``part`` defaulting to ``step % P``.  The cut is the
+    very last step, after k-hop (dataset/h5_dataset.py:232-233).  Node ids and per-part plans are kept per ``graph.traj_index``
+    in ``f.partition_cache``, computed from the first processed frame seen of a trajectory, as the reference's cache is;
+    later frames of a cached part cost one gather launch.  A trajectory of one part comes back untouched.  The parts carry no
+    ``face`` and no cut edges (see ``apply_partition``).  ``None`` leaves the callable as it is without the argument."""
+    if partitioning is not None:
+        partitioning = dict(partitioning)
+        unknown = set(partitioning) - {"num_partitions", "max_nodes_per_partition", "method", "seed"}
+        if unknown:
+            raise ValueError(f"partitioning: unknown keys {sorted(unknown)}")
+        num_partitions_for(1, partitioning.get("num_partitions"), partitioning.get("max_nodes_per_partition"))   # validates
     if isinstance(khop, bool) or not isinstance(khop, int) or khop < 1:
         raise ValueError(f"khop must be an integer >= 1, got {khop!r}")
     steps = []
@@ -274,4 +487,31 @@ def build_preprocessing(noise_parameters=None, world_pos_parameters=None, add_ed
             graph = f(graph, step) if len(inspect.signature(f).parameters) >= 2 else f(graph)
         return graph
 
-    return run
+    if partitioning is None:
+        return run
+
+    cache: dict = {}
+
+    def run_part(graph, step: int = 0, part: Optional[int] = None):
+        graph = run(graph, step)
+        P = num_partitions_for(_graph_num_nodes(graph), partitioning.get("num_partitions"), partitioning.get("max_nodes_per_partition"))
+        if P == 1:
+            return graph
+        p = int(step) % P if part is None else int(part)
+        if not 0 <= p < P:
+            raise ValueError(f"part must be in [0, {P}), got {p}")
+        traj = graph.traj_index
+        entry = cache.get(int(traj)) if traj is not None else None
+        if entry is None:
+            entry = {"node_ids": partition_node_ids(graph, P, method=partitioning.get("method", "auto"), seed=partitioning.get("seed", 0)),
+                     "plans": {}}
+            if traj is not None:
+                cache[int(traj)] = entry
+        plan = entry["plans"].get(p)
+        if plan is None:
+            plan = entry["plans"][p] = partition_plan(graph, entry["node_ids"][p])
+        return apply_partition(graph, None, plan=plan)
+
+    run_part.partition_cache = cache
+    run_part.partitioning = partitioning
+    return run_part

@@ -774,6 +774,51 @@ int mgn_khop_count(const int64_t* row0, const int64_t* row1, int64_t E, int64_t 
 int mgn_khop_fill(const void* ws, size_t ws_bytes, int64_t N, int hops, int64_t* out0, int64_t* out1, int64_t cap, void* stream);
 const char* mgn_khop_last_error(void);
 
+/* ================================================================================
+ * induced sub-meshes (training a mesh in parts) -- csrc/mgn_subgraph.hip
+ * ================================================================================
+ * torch_geometric.utils.subgraph(subset, edge_index, relabel_nodes=True) of torch-geometric 2.6.1 for an index subset, as the
+ * reference's Dataset applies it per sample (graphphysics/dataset/dataset.py:244-327): the edges whose two ends are both in
+ * node_ids[S], in INPUT ORDER, relabelled to the position in node_ids (which need not be sorted); duplicates and self loops
+ * of the input stay; edges with one end outside the subset (cut edges) are dropped.  The output size is not known in advance,
+ * so the call is split in two; everything the second half needs from the first lives in the caller's workspace:
+ *   mgn_subgraph_count  builds the relabel table (new_index[N] = -1, new_index[node_ids[i]] = i), relabels and flags every edge
+ *                       (one workgroup per mgn_subgraph_block_edges() consecutive edges), scans the per-workgroup counts and
+ *                       returns the number of kept edges in *n_edges_host (a HOST pointer).  Synchronises `stream` once for
+ *                       the result: topology preparation, not capturable.  Returns 3 when an entry of node_ids, src or dst
+ *                       is outside [0, N), 5 when node_ids lists a node twice (both found on the device; 3 wins).
+ *   mgn_subgraph_fill   ordered stream compaction (wave64 ballot ranks + a cross-wave scan in LDS; no atomics: the order is
+ *                       the input's and the result is bit-identical from run to run) into out_src / out_dst (relabelled) and
+ *                       out_edge_pos (each kept edge's position in the input: edge_attr rows, and every later frame of the
+ *                       same part, follow by a plain row gather), each int64 with room for `cap` >= the counted number (else 1
+ *                       before any launch).  out_edge_mask (uint8 [E], may be null) is PyG's edge_mask.  Reads the header
+ *                       mgn_subgraph_count left in `ws` (one small copy to the host).
+ * 0 <= N, S <= 2^31 - 2, 0 <= E <= 2^40; anything else, a null pointer with a non-zero count, or a workspace below
+ * mgn_subgraph_workspace_bytes(N, E) (which is 0 for sizes out of range) returns 1 before any launch.  2 = HIP error.
+ *
+ * mgn_gather_rows_batch: dst[r, :width] = src[idx[r], :width], r < rows, for up to MGN_MAX_GATHER_JOBS jobs in ONE launch;
+ * rows of 32-bit elements, any width >= 1, any leading dimensions >= width (in elements), 64-bit row counts and indices.  An
+ * index outside [0, src_rows) is not followed (that row of dst is left as it is).  Never synchronises: capturable. */
+#define MGN_MAX_GATHER_JOBS 8
+typedef struct {
+  const float* src;    /* [src_rows, ld_src] */
+  int64_t ld_src;
+  int64_t width;
+  const int64_t* idx;  /* [rows] */
+  int64_t rows;
+  float* dst;          /* [rows, ld_dst] */
+  int64_t ld_dst;
+  int64_t src_rows;
+} mgn_gather_job;
+size_t mgn_subgraph_workspace_bytes(int64_t N, int64_t E);
+int mgn_subgraph_block_edges(void);
+int mgn_subgraph_count(const int64_t* node_ids, int64_t S, int64_t N, const int64_t* src, const int64_t* dst, int64_t E,
+                       int64_t* n_edges_host, void* ws, size_t ws_bytes, void* stream);
+int mgn_subgraph_fill(const void* ws, size_t ws_bytes, int64_t E, int64_t* out_src, int64_t* out_dst, int64_t* out_edge_pos,
+                      uint8_t* out_edge_mask, int64_t cap, void* stream);
+int mgn_gather_rows_batch(int n_jobs, const mgn_gather_job* jobs, void* stream);
+const char* mgn_subgraph_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif

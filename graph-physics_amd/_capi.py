@@ -16,8 +16,9 @@ _REPO = os.path.dirname(_HERE)
 LIB_PATH = os.environ.get("MGN_LIB") or os.path.join(_CSRC, "libmgn_hip.so")
 SOURCES = [os.path.join(_CSRC, "mgn_kernels.hip"), os.path.join(_CSRC, "mgn_prep.hip"), os.path.join(_CSRC, "mgn_attn.hip"),
            os.path.join(_CSRC, "mgn_dense.hip"), os.path.join(_CSRC, "mgn_loss.hip"), os.path.join(_CSRC, "mgn_khop.hip"),
-           os.path.join(_CSRC, "mgn_subgraph.hip")]
-DEPS = [os.path.join(_CSRC, "mgn_x6.inc"), os.path.join(_CSRC, "mgn_fused.inc"), os.path.join(_CSRC, "mgn_pp.inc"), os.path.join(_CSRC, "mgn_ppr.inc")]  # included by the source
+           os.path.join(_CSRC, "mgn_subgraph.hip"), os.path.join(_CSRC, "mgn_randedge.hip")]
+DEPS = [os.path.join(_CSRC, "mgn_x6.inc"), os.path.join(_CSRC, "mgn_fused.inc"), os.path.join(_CSRC, "mgn_pp.inc"), os.path.join(_CSRC, "mgn_ppr.inc"),
+        os.path.join(_CSRC, "mgn_philox.inc")]  # included by the sources
 HEADER = os.path.join(_REPO, "include", "mgn_hip.h")
 # No packed-fp32 VALU (v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32) in device code: beside a SIMD partner that streams MFMAs
 # one of them takes ~70 cycles instead of ~6 (tools/coissue_probe.hip; plain VALU: 8), and hipcc forms them everywhere --
@@ -303,6 +304,11 @@ SYMBOLS = {
     "mgn_subgraph_fill": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "mgn_gather_rows_batch": (C.c_int, [C.c_int, C.POINTER(GatherJob), C.c_void_p]),
     "mgn_subgraph_last_error": (C.c_char_p, []),
+    "mgn_randedge_default_candidates": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64]),
+    "mgn_randedge_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
+    "mgn_randedge": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p,
+                               C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mgn_randedge_last_error": (C.c_char_p, []),
 }
 
 _lib = None
@@ -416,8 +422,8 @@ def lib():
 
 
 def check(rc: int, what: str, prep: bool = False, attn: bool = False, dense: bool = False, loss: bool = False, khop: bool = False,
-          subgraph: bool = False):
+          subgraph: bool = False, randedge: bool = False):
     if rc != 0:
-        fn = lib().mgn_subgraph_last_error if subgraph else lib().mgn_khop_last_error if khop else lib().mgn_loss_last_error if loss else lib().mgn_dense_last_error if dense else (lib().mgn_attn_last_error if attn else (lib().mgn_prep_last_error if prep else lib().mgn_last_error))
+        fn = lib().mgn_randedge_last_error if randedge else lib().mgn_subgraph_last_error if subgraph else lib().mgn_khop_last_error if khop else lib().mgn_loss_last_error if loss else lib().mgn_dense_last_error if dense else (lib().mgn_attn_last_error if attn else (lib().mgn_prep_last_error if prep else lib().mgn_last_error))
         msg = fn().decode("utf-8", "replace")
         raise RuntimeError(f"{what} failed (code {rc}): {msg}")

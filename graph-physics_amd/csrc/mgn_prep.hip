@@ -1133,17 +1133,7 @@ struct NoiseRanges {
   int col0[NOISE_MAX_RANGES + 1];  // prefix sums of the range widths
 };
 
-__device__ __forceinline__ void philox4x32_10(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t& r0,
-                                              uint32_t& r1) {
-#pragma unroll
-  for (int i = 0; i < 10; ++i) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-    c1 = (uint32_t)p1, c3 = (uint32_t)p0, c0 = n0, c2 = n2;
-    k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
-  }
-  r0 = c0, r1 = c1;
-}
+#include "mgn_philox.inc"  // philox4x32_10, shared with mgn_randedge.hip
 
 __global__ void __launch_bounds__(256) k_add_noise(float* __restrict__ x, int x_w, long N, const NoiseRanges R, int type_idx, uint64_t seed,
                                                   uint32_t offset) {

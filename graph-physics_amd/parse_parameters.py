@@ -26,7 +26,12 @@ def get_preprocessing(param: Dict[str, Any], device: torch.device, use_edge_feat
     (training/parse_parameters.py:224, dataset/dataset.py:206-242); the engine has no Dataset class, so the key is read
     here and the k-hop expansion becomes the last step of the callable, with a per-trajectory cache keyed by
     ``graph.traj_index``.  ``dataset.khop`` defaults to 1; a non-integer or a value below 1 is a ``ValueError``.
-    ``dataset.new_edges_ratio > 0`` (random extra edges) is not implemented and raises rather than train on another graph.
+    ``dataset.new_edges_ratio`` (random extra edges per sample, ``preprocess.add_random_edges``) is read here for the same
+    reason: ``None`` or 0 is off; a value in ``(0, 1]`` is handed on as ``new_edges_ratio`` when ``device`` is a GPU (``cuda``);
+    the sampler has no host path, so on any other device the key raises ``NotImplementedError`` when the callable is built
+    rather than at the first sample.  A non-number, a bool or a value outside ``[0, 1]`` is a ``ValueError`` (the reference
+    silently ignores a ratio above 1).  The reference freezes a frame's draw while the frame sits in its LRU frame cache; the
+    engine has no Dataset class and draws per ``(seed, step)``.
 
     ``use_partitioning`` with ``num_partitions`` or ``max_nodes_per_partition`` are the reference's ``get_dataset`` arguments
     of the same names (train.py ``--use_partitioning --num_partitions / --max_nodes_per_partition``): every sample becomes one
@@ -53,9 +58,16 @@ def get_preprocessing(param: Dict[str, Any], device: torch.device, use_edge_feat
     if isinstance(khop, bool) or not isinstance(khop, int) or khop < 1:
         raise ValueError(f"dataset.khop: an integer >= 1, got {khop!r}")
     ratio = dataset.get("new_edges_ratio", 0)
-    if ratio is not None and ratio > 0:
-        raise NotImplementedError("dataset.new_edges_ratio: random extra edges are not implemented by this engine")
+    if ratio is None:
+        ratio = 0
+    if isinstance(ratio, bool) or not isinstance(ratio, (int, float)) or not 0 <= ratio <= 1:
+        raise ValueError(f"dataset.new_edges_ratio: a number in [0, 1], got {ratio!r}")
     extra = {}
+    if ratio > 0:
+        if torch.device(device).type != "cuda":
+            raise NotImplementedError("dataset.new_edges_ratio: random extra edges are drawn by GPU kernels only (there is no host "
+                                      f"path); got device {str(device)!r}")
+        extra["new_edges_ratio"] = float(ratio)
     if use_partitioning:
         from .preprocess import num_partitions_for
 

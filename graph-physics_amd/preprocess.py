@@ -339,6 +339,148 @@ def partition_node_ids(graph, num_partitions: int, method: str = "auto", seed: i
     return [torch.from_numpy(np.nonzero(part == p)[0].astype(np.int64)).to(dev) for p in range(num_partitions)]
 
 
+# ----------------------------------------------------------------------------------------- random extra edges
+RANDEDGE_ROUNDS = 4
+
+
+def num_random_pairs(num_edges: int, p: float) -> int:
+    """K of ``add_random_edges``: ``round(E * p) // 2`` with Python's ``round`` (half to even), as PyG computes it"""
+    return round(int(num_edges) * p) // 2
+
+
+def random_edges_sparse(num_nodes: int, num_edges: int, num_pairs: int) -> bool:
+    """the regime predicate of ``add_random_edges``: ``4 (E + K) <= N (N - 1) / 2`` (every real mesh) -> the kernels"""
+    return 4 * (int(num_edges) + int(num_pairs)) <= int(num_nodes) * (int(num_nodes) - 1) // 2
+
+
+def random_edges_candidates(num_nodes: int, num_edges: int, num_pairs: int) -> int:
+    """M, the candidates drawn per round in the sparse regime: ``int(1.1 K / (1 - E / P)) + 64``"""
+    P = int(num_nodes) * (int(num_nodes) - 1) // 2
+    return int(1.1 * int(num_pairs) / (1 - int(num_edges) / P)) + 64
+
+
+_randedge_state: dict = {}   # per device index: {"flags": device int32[4], "pending": [(event, pinned host copy), ...]}
+
+
+def _randedge_raise(st, bits: int):
+    """the sticky device flag has been seen: clear it (one queued memset), forget older copies of it, raise"""
+    st["flags"].zero_()
+    torch.cuda.current_stream(st["flags"].device).synchronize()   # the error path may wait: later copies must not carry the bit again
+    st["pending"].clear()
+    if bits & 1:
+        raise IndexError("add_random_edges: edge_index has entries outside [0, num_nodes)")
+    if bits & 4:
+        raise RuntimeError("add_random_edges: the pair table of mgn_randedge overflowed")
+    raise RuntimeError("add_random_edges: fewer than K free pairs were found in %d rounds of candidates; the missing columns "
+                       "of that call's result hold node 0" % RANDEDGE_ROUNDS)
+
+
+def _randedge_check(st, wait: bool):
+    pending = st["pending"]
+    bits = 0
+    while pending and (wait or pending[0][0].query()):
+        ev, host = pending.pop(0)
+        if wait:
+            ev.synchronize()
+        bits |= int(host[0])
+    if bits:
+        _randedge_raise(st, bits)
+
+
+def random_edges_check(device=None) -> None:
+    """Look at the deferred error flag of earlier ``add_random_edges`` calls WITHOUT waiting: one event query per call whose
+    flag has not been read yet.  Raises what ``random_edges_resolve`` raises if a finished call reported an error."""
+    for idx, st in list(_randedge_state.items()):
+        if device is None or torch.device(device).index in (None, idx):
+            _randedge_check(st, wait=False)
+
+
+def random_edges_resolve(device=None) -> None:
+    """Wait for the deferred error flag of every ``add_random_edges`` call queued so far (on ``device``, default: all devices):
+    ``IndexError`` if an ``edge_index`` had entries outside ``[0, num_nodes)``, ``RuntimeError`` if a call came up short of K
+    pairs.  The flag is cleared when it is raised."""
+    for idx, st in list(_randedge_state.items()):
+        if device is None or torch.device(device).index in (None, idx):
+            _randedge_check(st, wait=True)
+
+
+def _random_edges_dense(ei: torch.Tensor, N: int, K: int, seed: int, offset: int) -> torch.Tensor:
+    """toy graphs (``P <= 6 E``): enumerate the P pairs, drop the occupied ones, pick ``min(K, free)`` without replacement.
+    Torch ops on the device, one host synchronisation; not a hot path."""
+    dev = ei.device
+    if bool(((ei < 0) | (ei >= N)).any()):
+        raise IndexError(f"edge_index has entries outside [0, {N})")
+    iu = torch.triu_indices(N, N, offset=1, device=dev)
+    lo, hi = torch.minimum(ei[0], ei[1]), torch.maximum(ei[0], ei[1])
+    occupied = (lo * N + hi)[lo != hi]
+    free = iu[:, ~torch.isin(iu[0] * N + iu[1], occupied)]
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(((int(seed) & (2 ** 64 - 1)) * 0x9E3779B97F4A7C15 + (int(offset) & 0xFFFFFFFF) + 0x45444745) % (2 ** 63))
+    n_free = int(free.shape[1])
+    pick = torch.randperm(n_free, generator=gen, device=dev)[:min(K, n_free)]
+    new = free[:, pick]
+    return torch.cat([ei, new, new.flip(0)], dim=1)
+
+
+def add_random_edges(edge_index: torch.Tensor, num_nodes: int, p: float, seed: int = 0, offset: int = 0,
+                     candidates_per_round: Optional[int] = None) -> torch.Tensor:
+    """``torch_geometric.utils.add_random_edge(edge_index, p, force_undirected=True)`` of torch-geometric 2.6 -- the "random
+    jumps" of the reference's ``Dataset._add_random_edges`` (dataset/dataset.py:171-203) -- on the device:
+    ``cat([edge_index, [[lo | hi], [hi | lo]]], dim=1)`` as int64, where the ``K = round(E * p) // 2`` new pairs ``lo < hi`` are
+    distinct, not yet edges in either direction and come in acceptance order.  ``K == 0`` or ``num_nodes < 2`` returns the input
+    object; ``p`` outside ``[0, 1]``, ``num_nodes >= 2^31`` or ``E >= 2^31`` is a ``ValueError``; a CPU tensor the usual
+    ``RuntimeError``.  The input may be unsorted and hold duplicates and self loops.
+
+    Deviation from PyG: a pair counts as occupied when EITHER direction is in the input (PyG looks at ``row < col`` entries
+    only); on the symmetric edge lists this pipeline makes the two rules agree.
+
+    The draw is a counter-based stream keyed by ``(seed, offset)`` (include/mgn_hip.h, ``mgn_randedge``) -- pass the training
+    step as ``offset`` -- pinned bit for bit by tests/randedge_reference.py; two calls with the same arguments give equal
+    tensors.  In the sparse regime (``random_edges_sparse``: every real mesh) the call is a fixed sequence of launches and does
+    NOT synchronise with the host.  What only the device knows -- an entry of ``edge_index`` outside ``[0, num_nodes)``
+    (``IndexError``), coming up short of K pairs (``RuntimeError``; probability below 1e-50 with the default number of
+    candidates per round) -- is raised by a LATER ``add_random_edges`` / ``random_edges_check`` call once the flag has arrived,
+    or by ``random_edges_resolve()``.  Denser toy graphs are sampled by enumeration with torch ops (one synchronisation,
+    ``K' = min(K, free pairs)``, errors raised at once; a ``torch.Generator`` seeded from ``(seed, offset)``)."""
+    if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0.0 <= p <= 1.0:
+        raise ValueError(f"p must be a number in [0, 1], got {p!r}")
+    if edge_index.dim() != 2 or edge_index.shape[0] != 2:
+        raise ValueError("edge_index must have shape [2, E]")
+    N, E = int(num_nodes), int(edge_index.shape[1])
+    if N >= 2 ** 31 or E >= 2 ** 31:
+        raise ValueError(f"add_random_edges: num_nodes = {N} / {E} edges are outside what the kernels index (< 2^31)")
+    _require_device(edge_index)
+    K = num_random_pairs(E, p)
+    if K == 0 or N < 2:
+        return edge_index
+    dev = edge_index.device
+    ei = edge_index if edge_index.dtype == torch.int64 and edge_index.is_contiguous() else edge_index.to(torch.int64).contiguous()
+    if not random_edges_sparse(N, E, K):
+        return _random_edges_dense(ei, N, K, seed, offset)
+    L = _capi.lib()
+    M = random_edges_candidates(N, E, K) if candidates_per_round is None else int(candidates_per_round)
+    nbytes = L.mgn_randedge_workspace_bytes(N, E, K, M)
+    if M < 1 or nbytes == 0:
+        raise ValueError(f"add_random_edges: {E} edges + {K} pairs + {M} candidates per round are outside what the kernels index")
+    with torch.cuda.device(dev):
+        idx = torch.cuda.current_device()
+        st = _randedge_state.get(idx)
+        if st is None:
+            st = _randedge_state[idx] = {"flags": torch.zeros(4, dtype=torch.int32, device=dev), "pending": []}
+        _randedge_check(st, wait=False)   # an earlier call's flag, if it has arrived
+        out = torch.empty(2, E + 2 * K, dtype=torch.int64, device=dev)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        rc = L.mgn_randedge(ei[0].data_ptr(), ei[1].data_ptr(), E, N, K, M, int(seed) & (2 ** 64 - 1), int(offset) & 0xFFFFFFFF,
+                            out[0].data_ptr(), out[1].data_ptr(), _ptr(st["flags"]), _ptr(ws), nbytes, _stream(dev))
+        _capi.check(rc, "mgn_randedge", randedge=True)
+        host = torch.empty(4, dtype=torch.int32, pin_memory=True)
+        host.copy_(st["flags"], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(dev))
+        st["pending"].append((ev, host))
+    return out
+
+
 def add_noise(graph, noise_index_start, noise_index_end, noise_scale, node_type_index: int, t: Optional[float] = None,
               seed: int = 0, offset: int = 0):
     """``add_noise`` of the reference (preprocessing.py:177-238), on the device and in place: Gaussian noise
@@ -402,7 +544,7 @@ def add_world_pos_features(graph, world_pos_index_start: int, world_pos_index_en
 
 def build_preprocessing(noise_parameters=None, world_pos_parameters=None, add_edges_features: bool = True,
                         extra_node_features=None, extra_edge_features=None, seed: int = 0, khop: int = 1,
-                        khop_cache: Optional[dict] = None, partitioning: Optional[dict] = None):
+                        khop_cache: Optional[dict] = None, partitioning: Optional[dict] = None, new_edges_ratio: float = 0.0):
     """Device-side ``build_preprocessing`` (preprocessing.py:380-444): the same transform ORDER as the
     reference -- extra node features, [obstacle next pos,] faces -> edges, [world edges,] edge features,
     noise inserted at position 1, extra edge features -- as one callable
@@ -422,7 +564,21 @@ def build_preprocessing(noise_parameters=None, world_pos_parameters=None, add_ed
     very last step, after k-hop (dataset/h5_dataset.py:232-233).  Node ids and per-part plans are kept per ``graph.traj_index``
     in ``f.partition_cache``, computed from the first processed frame seen of a trajectory, as the reference's cache is;
     later frames of a cached part cost one gather launch.  A trajectory of one part comes back untouched.  The parts carry no
-    ``face`` and no cut edges (see ``apply_partition``).  ``None`` leaves the callable as it is without the argument."""
+    ``face`` and no cut edges (see ``apply_partition``).  ``None`` leaves the callable as it is without the argument.
+
+    ``new_edges_ratio`` in ``(0, 1]`` appends the reference's random extra edges (``add_random_edges``; ``Dataset.
+    _add_random_edges``) after k-hop and before the partition cut, the reference's order (dataset/h5_dataset.py:184-187,
+    232-233): every sample gets ``round(E * ratio) // 2`` new node pairs in both directions, drawn with ``seed`` = this
+    callable's ``seed`` and ``offset = step``, so a ``(seed, step)`` names its draw and consecutive steps differ.  With
+    ``add_edges_features`` ``edge_attr`` is then recomputed on ALL edges as mesh-space Cartesian + Distance (earlier extra
+    edge columns are dropped, as the reference's ``edge_attr = None`` -> Compose does); without, it is ``None``.  The k-hop
+    cache keeps the un-augmented tensors.  The step does not synchronise with the host; at its start the deferred error flag
+    of the previous step is looked at with one event query (``random_edges_check``).  With ``partitioning`` the node ids stay
+    cached per trajectory but the per-part plans cannot be (they hold the cut edge list, and the edges now change every
+    step): every sample is cut with ``subgraph`` as the reference does and PAYS ITS ONE HOST SYNCHRONISATION per sample;
+    ``partition_cache[traj]["plans"]`` stays empty.  The default 0.0 leaves the callable as it is without the argument."""
+    if isinstance(new_edges_ratio, bool) or not isinstance(new_edges_ratio, (int, float)) or not 0.0 <= new_edges_ratio <= 1.0:
+        raise ValueError(f"new_edges_ratio must be a number in [0, 1], got {new_edges_ratio!r}")
     if partitioning is not None:
         partitioning = dict(partitioning)
         unknown = set(partitioning) - {"num_partitions", "max_nodes_per_partition", "method", "seed"}
@@ -480,6 +636,13 @@ def build_preprocessing(noise_parameters=None, world_pos_parameters=None, add_ed
                 khop_cache[traj] = (g.edge_index, g.edge_attr)
             return g
         steps.append(k_hop)
+    if new_edges_ratio > 0:
+        def random_edges(g, step):
+            random_edges_check(g.edge_index.device)
+            g.edge_index = add_random_edges(g.edge_index, _graph_num_nodes(g), new_edges_ratio, seed=seed, offset=step)
+            g.edge_attr = edge_features(g.pos, g.edge_index) if add_edges_features else None
+            return g
+        steps.append(random_edges)
 
     def run(graph, step: int = 0):
         import inspect
@@ -507,6 +670,8 @@ def build_preprocessing(noise_parameters=None, world_pos_parameters=None, add_ed
                      "plans": {}}
             if traj is not None:
                 cache[int(traj)] = entry
+        if new_edges_ratio > 0:   # the edges are this sample's own: nothing of the cut can be kept
+            return apply_partition(graph, entry["node_ids"][p])
         plan = entry["plans"].get(p)
         if plan is None:
             plan = entry["plans"][p] = partition_plan(graph, entry["node_ids"][p])

@@ -819,6 +819,49 @@ int mgn_subgraph_fill(const void* ws, size_t ws_bytes, int64_t E, int64_t* out_s
 int mgn_gather_rows_batch(int n_jobs, const mgn_gather_job* jobs, void* stream);
 const char* mgn_subgraph_last_error(void);
 
+/* ================================================================================
+ * random extra edges (the config key dataset.new_edges_ratio) -- csrc/mgn_randedge.hip
+ * ================================================================================
+ * torch_geometric.utils.add_random_edge(edge_index, p, force_undirected=True) of torch-geometric 2.6, as the reference's
+ * Dataset applies it per sample (graphphysics/dataset/dataset.py:171-203): K = round(E p) // 2 (the caller's arithmetic) random
+ * node pairs that are not yet edges, appended in both directions.  out0 / out1 (int64, room for E + 2 K each) receive
+ *   [ the E input columns, untouched and in order | the K new pairs (lo, hi), lo < hi, in acceptance order | the same, (hi, lo) ].
+ * A pair {i, j}, i < j, is OCCUPIED when the input holds (i, j) or (j, i) (PyG looks at row < col entries only; on a symmetric
+ * edge list the two rules agree).  Self loops and duplicates of the input are allowed and occupy nothing extra.  New pairs are
+ * distinct, never occupied, never self loops.
+ *
+ * The stream is counter-based, so that any implementation can reproduce it (tests/randedge_reference.py does, in numpy).  Up to
+ * MGN_RANDEDGE_ROUNDS rounds of M candidates; candidate c of round r takes
+ *   (r0, r1, ..) = Philox4x32-10(key = (seed_lo, seed_hi ^ 0x45444745), counter = (c_lo, c_hi, r, offset))
+ *   a = (r0 * N) >> 32,  b = (r1 * N) >> 32          (multiply-shift: a bias of at most N / 2^32 per id, accepted)
+ * -- the key tweak keeps it apart from mgn_add_noise's stream of the same seed and offset -- and is REJECTED if a == b;
+ * otherwise lo = min(a, b), hi = max(a, b), code = lo * N + hi.  It is ACCEPTED if it is not rejected, its pair is not occupied,
+ * its code was not accepted in an earlier round and it is the lowest-indexed candidate of its round with that code.  Accepted
+ * candidates are taken in (round, candidate index) order until K are in -- never in the order of their codes, which would favour
+ * low node ids.  M = 0 means mgn_randedge_default_candidates(N, E, K) = (int64)(1.1 * K / (1 - E / P)) + 64 in double arithmetic,
+ * P = N (N - 1) / 2; with it, coming up short after the last round has a probability below 1e-50.
+ *
+ * The launch sequence is fixed (every round is queued; a round whose device-side count has reached K leaves at once), the
+ * output shape is known to the host, and the call NEVER synchronises: capturable.  Slots are given out by ordered stream
+ * compaction, so two calls give identical results.  What only the device can know is reported through flags[0] (device int,
+ * bits are OR-ed in and never cleared here: the caller zeroes it once and reads it when it likes):
+ *   MGN_RANDEDGE_ERR_RANGE  an entry of row0 / row1 lies outside [0, N): it is copied through but not followed
+ *   MGN_RANDEDGE_ERR_SHORT  fewer than K pairs were accepted: the remaining new columns hold 0 (written before the rounds run, so
+ *                           every id of the output is in range)
+ *   MGN_RANDEDGE_ERR_TABLE  the pair table overflowed (it is sized so that it cannot)
+ * Sparse regime only: 4 (E + K) <= P.  2 <= N < 2^31, 1 <= E < 2^31, 1 <= K <= E, 0 <= M < 2^30, E + K + M within the 2^31
+ * slots of the pair table; anything else, a null pointer, or a workspace below mgn_randedge_workspace_bytes(N, E, K, M) (which is
+ * 0 for arguments out of range) returns 1 before any launch.  2 = HIP error.  mgn_randedge_last_error(). */
+#define MGN_RANDEDGE_ROUNDS 4
+#define MGN_RANDEDGE_ERR_RANGE 1
+#define MGN_RANDEDGE_ERR_SHORT 2
+#define MGN_RANDEDGE_ERR_TABLE 4
+int64_t mgn_randedge_default_candidates(int64_t N, int64_t E, int64_t K);
+size_t mgn_randedge_workspace_bytes(int64_t N, int64_t E, int64_t K, int64_t M);
+int mgn_randedge(const int64_t* row0, const int64_t* row1, int64_t E, int64_t N, int64_t K, int64_t M, uint64_t seed, uint32_t offset,
+                 int64_t* out0, int64_t* out1, int* flags, void* ws, size_t ws_bytes, void* stream);
+const char* mgn_randedge_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif

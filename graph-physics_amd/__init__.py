@@ -12,5 +12,7 @@ from .losses import (LossType, MultiLoss, L2Loss, CosineLoss, L1SmoothLoss, Grad
                      DivergenceL1Loss, DivergenceL1SmoothLoss, LossGeometry, compute_gradient)
 from .ops import set_matrix_precision, get_matrix_precision, set_node_renumbering, get_node_renumbering  # noqa: F401
 from . import preprocess  # noqa: F401
+from .preprocess import knn, knn_graph, min_distance_to_type  # noqa: F401
+from .hierarchical_pooling import DownSampler, UpSampler, knn_interpolate  # noqa: F401
 
 __version__ = "0.1.0"

@@ -16,7 +16,7 @@ _REPO = os.path.dirname(_HERE)
 LIB_PATH = os.environ.get("MGN_LIB") or os.path.join(_CSRC, "libmgn_hip.so")
 SOURCES = [os.path.join(_CSRC, "mgn_kernels.hip"), os.path.join(_CSRC, "mgn_prep.hip"), os.path.join(_CSRC, "mgn_attn.hip"),
            os.path.join(_CSRC, "mgn_dense.hip"), os.path.join(_CSRC, "mgn_loss.hip"), os.path.join(_CSRC, "mgn_khop.hip"),
-           os.path.join(_CSRC, "mgn_subgraph.hip"), os.path.join(_CSRC, "mgn_randedge.hip")]
+           os.path.join(_CSRC, "mgn_subgraph.hip"), os.path.join(_CSRC, "mgn_randedge.hip"), os.path.join(_CSRC, "mgn_knn.hip")]
 DEPS = [os.path.join(_CSRC, "mgn_x6.inc"), os.path.join(_CSRC, "mgn_fused.inc"), os.path.join(_CSRC, "mgn_pp.inc"), os.path.join(_CSRC, "mgn_ppr.inc"),
         os.path.join(_CSRC, "mgn_philox.inc")]  # included by the sources
 HEADER = os.path.join(_REPO, "include", "mgn_hip.h")
@@ -309,6 +309,15 @@ SYMBOLS = {
     "mgn_randedge": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p,
                                C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "mgn_randedge_last_error": (C.c_char_p, []),
+    "mgn_knn_max_k": (C.c_int, []),
+    "mgn_knn_tile_points": (C.c_int, []),
+    "mgn_knn_search": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
+                                 C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mgn_knn_interp_fwd": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
+                                     C.c_void_p]),
+    "mgn_knn_interp_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p,
+                                     C.c_void_p]),
+    "mgn_knn_last_error": (C.c_char_p, []),
 }
 
 _lib = None
@@ -422,8 +431,8 @@ def lib():
 
 
 def check(rc: int, what: str, prep: bool = False, attn: bool = False, dense: bool = False, loss: bool = False, khop: bool = False,
-          subgraph: bool = False, randedge: bool = False):
+          subgraph: bool = False, randedge: bool = False, knn: bool = False):
     if rc != 0:
-        fn = lib().mgn_randedge_last_error if randedge else lib().mgn_subgraph_last_error if subgraph else lib().mgn_khop_last_error if khop else lib().mgn_loss_last_error if loss else lib().mgn_dense_last_error if dense else (lib().mgn_attn_last_error if attn else (lib().mgn_prep_last_error if prep else lib().mgn_last_error))
+        fn = lib().mgn_knn_last_error if knn else lib().mgn_randedge_last_error if randedge else lib().mgn_subgraph_last_error if subgraph else lib().mgn_khop_last_error if khop else lib().mgn_loss_last_error if loss else lib().mgn_dense_last_error if dense else (lib().mgn_attn_last_error if attn else (lib().mgn_prep_last_error if prep else lib().mgn_last_error))
         msg = fn().decode("utf-8", "replace")
         raise RuntimeError(f"{what} failed (code {rc}): {msg}")

@@ -680,3 +680,154 @@ def build_preprocessing(noise_parameters=None, world_pos_parameters=None, add_ed
     run_part.partition_cache = cache
     run_part.partitioning = partitioning
     return run_part
+
+
+# ------------------------------------------------------------------------------------------------ k nearest neighbours
+def _host_ptr(ptr, n: int, what: str):
+    """segment offsets given on the host (list / tuple / CPU tensor) as a checked list of ints"""
+    p = [int(v) for v in (ptr.tolist() if torch.is_tensor(ptr) else ptr)]
+    if len(p) < 2 or p[0] != 0 or p[-1] != n or any(b < a for a, b in zip(p, p[1:])):
+        raise ValueError(f"{what} must be non-decreasing offsets from 0 to the number of points ({n}), got {p[:8]}{'...' if len(p) > 8 else ''}")
+    return p
+
+
+def _knn_segments(nx: int, ny: int, batch_x, batch_y, ptr_x, ptr_y, dev):
+    """(ptr_x, ptr_y, nseg, host_x, host_y): the two offset vectors as device int64 [nseg + 1]; host_* are the same offsets as
+    lists where the host knows them (given as ``ptr_*``, or a side without ``batch`` and ``ptr``: all of it is segment 0), else
+    None.  Synchronises once -- to read the number of segments -- only when no ``ptr_*`` is given and a ``batch_*`` is."""
+    sides = []
+    for n, batch, ptr, what in ((nx, batch_x, ptr_x, "ptr_x"), (ny, batch_y, ptr_y, "ptr_y")):
+        if ptr is not None and torch.is_tensor(ptr) and ptr.is_cuda:
+            sides.append(("dev", ptr.to(torch.int64).contiguous()))
+        elif ptr is not None:
+            sides.append(("host", _host_ptr(ptr, n, what)))
+        elif batch is not None and n > 0:
+            sides.append(("batch", batch))
+        else:
+            sides.append(("none", n))
+    lens = {(s[1].numel() if s[0] == "dev" else len(s[1])) - 1 for s in sides if s[0] in ("dev", "host")}
+    if len(lens) > 1:
+        raise ValueError("ptr_x and ptr_y must describe the same number of segments")
+    if lens:
+        nseg = lens.pop()
+    elif any(s[0] == "batch" for s in sides):
+        nseg = int(torch.stack([s[1][-1] for s in sides if s[0] == "batch"]).max()) + 1   # the one synchronisation
+    else:
+        nseg = 1
+    if nseg < 1:
+        raise ValueError("at least one segment is needed")
+    dev_ptr, host = [], []
+    for kind, v in sides:
+        if kind == "none":
+            kind, v = "host", [0] + [v] * nseg
+        if kind == "host":
+            dev_ptr.append(torch.tensor(v, dtype=torch.int64, device=dev))
+            host.append(v)
+        elif kind == "dev":
+            dev_ptr.append(v)
+            host.append(None)
+        else:
+            b = v.to(torch.int64).contiguous()
+            dev_ptr.append(torch.searchsorted(b, torch.arange(nseg + 1, dtype=torch.int64, device=dev)))
+            host.append(None)
+    return dev_ptr[0], dev_ptr[1], nseg, host[0], host[1]
+
+
+def _knn_search(pos_x: torch.Tensor, pos_y: torch.Tensor, k: int, ptr_x: torch.Tensor, ptr_y: torch.Tensor, nseg: int,
+                exclude_self: bool = False):
+    """(idx [ny, k] int64, d2 [ny, k] fp32) of ``mgn_knn_search`` (include/mgn_hip.h): nearest first by (d2, index), ``-1`` /
+    ``+inf`` where the segment runs out of references.  ``ptr_*`` are device offsets.  Never synchronises."""
+    _require_device(pos_x, pos_y, ptr_x, ptr_y)
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+        raise ValueError(f"k must be an integer >= 1, got {k!r}")
+    L = _capi.lib()
+    if k > L.mgn_knn_max_k():
+        raise ValueError(f"k must not exceed {L.mgn_knn_max_k()}, got {k}")
+    if pos_x.dim() != 2 or pos_y.dim() != 2 or pos_x.shape[1] != pos_y.shape[1] or pos_x.shape[1] not in (2, 3):
+        raise ValueError("positions must be [n, 2] or [n, 3], the same width on both sides")
+    dev = pos_y.device
+    x, y = pos_x.detach().to(torch.float32).contiguous(), pos_y.detach().to(torch.float32).contiguous()
+    nx, ny, D = int(x.shape[0]), int(y.shape[0]), int(x.shape[1])
+    idx = torch.empty(ny, k, dtype=torch.int64, device=dev)
+    d2 = torch.empty(ny, k, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.mgn_knn_search(_ptr(x), nx, _ptr(y), ny, D, k, _ptr(ptr_x), _ptr(ptr_y), nseg, 1 if exclude_self else 0, _ptr(idx), _ptr(d2),
+                              _stream(dev))
+    _capi.check(rc, "mgn_knn_search", knn=True)
+    return idx, d2
+
+
+def _always_k(host_x, host_y, k: int, exclude_self: bool) -> bool:
+    """True where the host can tell that no slot stays empty: every segment with a query holds k admissible references"""
+    if host_x is None or host_y is None:
+        return False
+    need = k + (1 if exclude_self else 0)
+    return all(host_x[s + 1] - host_x[s] >= need for s in range(len(host_y) - 1) if host_y[s + 1] > host_y[s])
+
+
+def knn(pos_x: torch.Tensor, pos_y: torch.Tensor, k: int, batch_x: Optional[torch.Tensor] = None, batch_y: Optional[torch.Tensor] = None,
+        ptr_x=None, ptr_y=None) -> torch.Tensor:
+    """``torch_cluster.knn``: for every point of ``pos_y`` its ``k`` nearest points of ``pos_x`` within the same graph of the
+    batch, as ``assign_index [2, M]`` int64 with rows (query, reference), grouped by query, nearest first; ties in the squared
+    fp32 distance go to the lower reference index.  A graph with fewer than ``k`` references gives fewer entries.  Exact
+    brute force on the device (csrc/mgn_knn.hip), 2-D or 3-D, ``k <= 32``; ``batch_*`` must be sorted.
+
+    Synchronisation: with ``ptr_x`` / ``ptr_y`` (``nseg + 1`` offsets as a list or a CPU tensor) or with no batch at all the
+    search never synchronises, and the result is returned without one where the offsets show that every graph holds ``k``
+    references.  With only ``batch_*`` the number of graphs is read once from the device (one synchronisation), and dropping
+    the empty slots sizes the result on the device (torch's boolean mask: it synchronises)."""
+    _require_device(pos_x, pos_y, batch_x, batch_y)
+    dev = pos_y.device
+    px, py, nseg, hx, hy = _knn_segments(int(pos_x.shape[0]), int(pos_y.shape[0]), batch_x, batch_y, ptr_x, ptr_y, dev)
+    idx, _ = _knn_search(pos_x, pos_y, k, px, py, nseg)
+    q = torch.arange(idx.shape[0], dtype=torch.int64, device=dev).repeat_interleave(k)
+    r = idx.reshape(-1)
+    if not _always_k(hx, hy, k, False):
+        keep = r >= 0
+        q, r = q[keep], r[keep]
+    return torch.stack([q, r])
+
+
+def knn_graph(pos: torch.Tensor, k: int, batch: Optional[torch.Tensor] = None, loop: bool = False, flow: str = "source_to_target",
+              force_undirected: bool = False, ptr=None) -> torch.Tensor:
+    """``torch_cluster.knn_graph`` / PyG ``KNNGraph``: edges from every node's ``k`` nearest nodes of its graph to the node,
+    ``[2, E]`` int64 with rows (neighbour, centre) (``flow="target_to_source"``: (centre, neighbour)), grouped by centre,
+    nearest first.  Without ``loop`` a node is never its own neighbour: the search leaves out the node ITSELF (by index), so
+    coincident nodes are neighbours of each other and cost no real neighbour -- upstream searches ``k + 1`` and drops whichever
+    entry is the node.  ``force_undirected`` (``KNNGraph(k, force_undirected=True)``): both directions of every edge, each pair
+    once, sorted by (row 0, row 1).  ``ptr`` (host offsets) instead of ``batch`` avoids the synchronisation that reads the
+    number of graphs; ``force_undirected`` and graphs smaller than ``k`` size their result on the device and synchronise."""
+    if flow not in ("source_to_target", "target_to_source"):
+        raise ValueError(f"flow must be 'source_to_target' or 'target_to_source', got {flow!r}")
+    _require_device(pos, batch)
+    dev = pos.device
+    N = int(pos.shape[0])
+    px, py, nseg, hx, hy = _knn_segments(N, N, batch, batch, ptr, ptr, dev)
+    idx, _ = _knn_search(pos, pos, k, px, py, nseg, exclude_self=not loop)
+    ctr = torch.arange(N, dtype=torch.int64, device=dev).repeat_interleave(k)
+    nbr = idx.reshape(-1)
+    if not _always_k(hx, hy, k, not loop):
+        keep = nbr >= 0
+        ctr, nbr = ctr[keep], nbr[keep]
+    row, col = (nbr, ctr) if flow == "source_to_target" else (ctr, nbr)
+    if force_undirected:   # to_undirected: both directions, coalesced
+        key = torch.unique(torch.cat([row * N + col, col * N + row]))   # sorted
+        return torch.stack([torch.div(key, N, rounding_mode="floor"), key % N]) if N > 0 else torch.stack([row, col])
+    return torch.stack([row, col])
+
+
+def min_distance_to_type(graph, target_type, node_types: torch.Tensor) -> torch.Tensor:
+    """``compute_min_distance_to_type`` of the reference (dataset/preprocessing.py:241-274): for every node the distance to the
+    nearest node whose entry of ``node_types`` equals ``target_type``, ``[N]`` fp32, over the whole graph (``batch`` is
+    ignored, as upstream).  The square root of the ``k = 1`` search: no ``[N, M, 3]`` intermediate.  A type without a node is a
+    ``ValueError``.  Selecting the nodes of the type sizes a tensor on the device: one synchronisation."""
+    pos = graph.pos
+    _require_device(pos, node_types)
+    target = pos[node_types.reshape(-1) == int(target_type)]
+    if target.shape[0] == 0:
+        raise ValueError(f"no node of type {target_type!r} in the graph")
+    dev = pos.device
+    px = torch.tensor([0, int(target.shape[0])], dtype=torch.int64, device=dev)
+    py = torch.tensor([0, int(pos.shape[0])], dtype=torch.int64, device=dev)
+    _, d2 = _knn_search(target, pos, 1, px, py, 1)
+    return torch.sqrt(d2[:, 0])

@@ -862,6 +862,45 @@ int mgn_randedge(const int64_t* row0, const int64_t* row1, int64_t E, int64_t N,
                  int64_t* out0, int64_t* out1, int* flags, void* ws, size_t ws_bytes, void* stream);
 const char* mgn_randedge_last_error(void);
 
+/* ================================================================================
+ * exact k-nearest-neighbour search and inverse-distance interpolation (multigrid pooling) -- csrc/mgn_knn.hip
+ * ================================================================================
+ * What PyG's KNNGraph / knn_interpolate (both on torch_cluster.knn) give the reference's DownSampler / UpSampler
+ * (graphphysics/models/hierarchical_pooling.py) and what its compute_min_distance_to_type needs.
+ *
+ * mgn_knn_search: brute-force k-NN of ny query points y [ny, dim] against nx reference points x [nx, dim] (fp32, row-major,
+ * dim 2 or 3), restricted to equal segments (graphs of a batch): both point sets are grouped by segment, ptr_x / ptr_y are
+ * DEVICE arrays of nseg + 1 int64 offsets (ptr[0] = 0, ptr[nseg] = n, non-decreasing; values are clamped to that on the device,
+ * never followed outside the arrays).  The result is pinned bit for bit:
+ *   d2(y, x)  = ((dx*dx) + (dy*dy)) + (dz*dz) in fp32, every operation rounded once (no FMA); in 2-D the last term is absent;
+ *   order     = ascending (d2, reference index): equal distances resolve to the lower index, whatever the tile or grid shape;
+ *   output    = idx [ny, k] int64 (GLOBAL reference indices) and d2 [ny, k] fp32, nearest first; where the query's segment
+ *               holds fewer than k (admissible) references the remaining slots are idx = -1, d2 = +inf;
+ *   exclude_self (for x is y) drops the reference whose global index equals the query's -- not "the nearest one", so
+ *               coincident points never cost a real neighbour.
+ * A reference at a NaN or infinite distance is never selected.  1 <= k <= mgn_knn_max_k() (32); mgn_knn_tile_points() is the
+ * number of reference points per LDS tile (for tests that straddle it).  ny == 0 and empty segments are not errors.  Never
+ * synchronises, needs no workspace: capturable.
+ *
+ * mgn_knn_interp_fwd: out[y, :] = sum_j a[y, j] * x[idx[y, j], :] over the slots with idx >= 0, a[y, j] = w_j / sum_j w_j,
+ * w_j = 1 / max(d2[y, j], 1e-16) (torch_geometric 2.6.1 knn_interpolate); fp32, accumulated in slot order j = 0 .. k-1 with one
+ * fma per slot.  x [nx, F], out [ny, F], any F >= 1; a [ny, k] is written for the backward (0 in the -1 slots).
+ * mgn_knn_interp_bwd: dx[c, :] = sum over the slots s = y * k + j with idx = c of a[s] * dy[y, :], as a segment sum over the CSR
+ * (rowptr [>= nx + 1], perm: slot numbers, int32, as mgn_csr_build groups the flattened idx) -- no atomics, identical bits from
+ * run to run; a reference nobody selected gets exactly 0.  Positions take no gradient: the weights are constants of the geometry.
+ *
+ * nx, ny, ny * k <= 2^31 - 1.  dim outside {2, 3}, k < 1, k > mgn_knn_max_k(), nseg < 1, F < 1, a null pointer with a non-zero
+ * count: 1 before any launch, text in mgn_knn_last_error().  2 = HIP error. */
+int mgn_knn_max_k(void);
+int mgn_knn_tile_points(void);
+int mgn_knn_search(const float* x, int64_t nx, const float* y, int64_t ny, int dim, int k, const int64_t* ptr_x, const int64_t* ptr_y,
+                   int64_t nseg, int exclude_self, int64_t* idx, float* d2, void* stream);
+int mgn_knn_interp_fwd(const float* x, int64_t nx, int F, const int64_t* idx, const float* d2, int64_t ny, int k, float* a, float* out,
+                       void* stream);
+int mgn_knn_interp_bwd(const float* dy, const float* a, const int32_t* rowptr, const int32_t* perm, int64_t nx, int64_t ny, int k, int F,
+                       float* dx, void* stream);
+const char* mgn_knn_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -833,8 +833,8 @@ class MlpFunction(torch.autograd.Function):
         Ws = [_f32c(params[2 * l]) for l in range(NL)]
         bs = [_f32c(params[2 * l + 1]) for l in range(NL)]
         scale = _f32c(params[2 * NL]) if has_norm else None
-        if NL < 2:
-            raise AssertionError("The MLP must have at least 2 layers (input and output).")
+        if NL < 2 or NL > _capi.MAX_LAYERS:
+            raise AssertionError("The MLP must have at least 2 layers (input and output)." if NL < 2 else f"at most {_capi.MAX_LAYERS} layers per MLP")
         M, kin = x.shape
         H = Ws[0].shape[0]
         out_w = Ws[-1].shape[0]
@@ -889,7 +889,7 @@ class MlpFunction(torch.autograd.Function):
             units = [pk.data_ptr() + u * _capi.WPACK_BYTES for u in range(NL)]
             wpack([(Wk[l].data_ptr(), H, False, units[l]) for l in range(NL)], dev)
             mlp_fwd(M, H, [(x, None, H)], Wk, bk, scale, out_w, None, y, None, saveH, U, R, wpk=units, saveM=Ms, saveZ=Zs, act=act)
-        else:
+        elif M > 0:   # (no rows: nothing to launch; mgn_mlp_fwd would judge SiLU at H = 128 by the LDS kernels this call never takes)
             mlp_fwd(M, H, [(x, None, kin)], Wk, bk, scale, out_w, None, y, None, saveH, U, R, act=act, saveZ=Zs, precision=prec)
         ctx.meta = (NL, H, kin, out_w, has_norm, kp != kin, op != out_w, act, mode)
         ctx.prec, ctx.Wk_rounded = prec, (Wk if prec else None)
@@ -940,7 +940,7 @@ class MlpFunction(torch.autograd.Function):
             din = [(None, None, dx)] if want_dx else []
             mlp_bwd(M, H, NL, dy, None, None, out_w, U, R, scale, saveH, [None] * NL, dZ, din, [None] * NL, dscale,
                     wpk=units, Ms=Ms, Zs=Zs, act=act)
-        else:
+        elif M > 0:
             # W^T operands of the generic chain: the H x H ones in ONE batched transpose launch (a torch transpose + copy each before)
             sq = [l for l in range(1, NL) if tuple(Wk[l].shape) == (H, H) and Wk[l].is_contiguous()]
             wt_buf = torch.empty(len(sq), H, H, **f) if sq else None

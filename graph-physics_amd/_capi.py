@@ -18,7 +18,7 @@ SOURCES = [os.path.join(_CSRC, "mgn_kernels.hip"), os.path.join(_CSRC, "mgn_prep
            os.path.join(_CSRC, "mgn_dense.hip"), os.path.join(_CSRC, "mgn_loss.hip"), os.path.join(_CSRC, "mgn_khop.hip"),
            os.path.join(_CSRC, "mgn_subgraph.hip"), os.path.join(_CSRC, "mgn_randedge.hip"), os.path.join(_CSRC, "mgn_knn.hip")]
 DEPS = [os.path.join(_CSRC, "mgn_x6.inc"), os.path.join(_CSRC, "mgn_fused.inc"), os.path.join(_CSRC, "mgn_pp.inc"), os.path.join(_CSRC, "mgn_ppr.inc"),
-        os.path.join(_CSRC, "mgn_philox.inc")]  # included by the sources
+        os.path.join(_CSRC, "mgn_philox.inc"), os.path.join(_CSRC, "mgn_host.inc"), os.path.join(_CSRC, "mgn_graphprim.inc")]  # included by the sources
 HEADER = os.path.join(_REPO, "include", "mgn_hip.h")
 # No packed-fp32 VALU (v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32) in device code: beside a SIMD partner that streams MFMAs
 # one of them takes ~70 cycles instead of ~6 (tools/coissue_probe.hip; plain VALU: 8), and hipcc forms them everywhere --
@@ -432,7 +432,11 @@ def lib():
 
 def check(rc: int, what: str, prep: bool = False, attn: bool = False, dense: bool = False, loss: bool = False, khop: bool = False,
           subgraph: bool = False, randedge: bool = False, knn: bool = False):
+    """Raise on a non-zero return code with the message of the translation unit the call lives in: the flag that is set names
+    it (mgn_<flag>_last_error; of several the last in the signature wins), none means mgn_kernels.hip (mgn_last_error)."""
     if rc != 0:
-        fn = lib().mgn_knn_last_error if knn else lib().mgn_randedge_last_error if randedge else lib().mgn_subgraph_last_error if subgraph else lib().mgn_khop_last_error if khop else lib().mgn_loss_last_error if loss else lib().mgn_dense_last_error if dense else (lib().mgn_attn_last_error if attn else (lib().mgn_prep_last_error if prep else lib().mgn_last_error))
+        flags = locals()
+        units = [u for u in ("prep", "attn", "dense", "loss", "khop", "subgraph", "randedge", "knn") if flags[u]]
+        fn = getattr(lib(), f"mgn_{units[-1]}_last_error" if units else "mgn_last_error")
         msg = fn().decode("utf-8", "replace")
         raise RuntimeError(f"{what} failed (code {rc}): {msg}")

@@ -19,20 +19,8 @@
 #include <stdlib.h>
 #include "mgn_hip.h"
 
-static thread_local char g_aerr[256] = "";
-extern "C" const char* mgn_attn_last_error(void) { return g_aerr; }
-static int afail(int code, const char* msg) {
-  snprintf(g_aerr, sizeof(g_aerr), "%s", msg);
-  return code;
-}
-static int acheck(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    snprintf(g_aerr, sizeof(g_aerr), "%s: %s", what, hipGetErrorString(e));
-    return 2;
-  }
-  return 0;
-}
+#include "mgn_host.inc"  // g_err, fail, check_launch
+extern "C" const char* mgn_attn_last_error(void) { return g_err; }
 
 // Lane l of a row group holds features 4l .. 4l+3; feature f belongs to head f % NH.  head_reduce turns the
 // per-feature partial products p[r] into the full per-HEAD sums, delivered to every lane for the heads of
@@ -515,11 +503,11 @@ static AttnLd attn_dense_ld(int H) { return AttnLd{H, H, H, H, H, H}; }
 static int attn_fwd_any(int b16, const float* q, const void* k, const void* v, const int32_t* rowptr, const int32_t* col, int64_t N, int H,
                         int num_heads, float* y, float* lse, float* y_raw, AttnLd ld, void* stream, const char* who) {
   if (!attn_args_ok(N, H, num_heads)) {
-    snprintf(g_aerr, sizeof(g_aerr), "%s: hidden must be 16/32/64/128 and num_heads 1/2/4/8/16 dividing it", who);
+    snprintf(g_err, sizeof(g_err), "%s: hidden must be 16/32/64/128 and num_heads 1/2/4/8/16 dividing it", who);
     return 1;
   }
   if (!attn_ld_ok(ld, H, false)) {
-    snprintf(g_aerr, sizeof(g_aerr), "%s: row pitches must be multiples of 4 elements and >= hidden", who);
+    snprintf(g_err, sizeof(g_err), "%s: row pitches must be multiples of 4 elements and >= hidden", who);
     return 1;
   }
   if (N == 0) return 0;
@@ -531,7 +519,7 @@ static int attn_fwd_any(int b16, const float* q, const void* k, const void* v, c
     ATTN_DISPATCH(k_attn_fwd, 2, q, k, v, rowptr, col, (long)N, num_heads, scale, sd, y, lse, y_raw, ld);
   else
     ATTN_DISPATCH(k_attn_fwd, 0, q, k, v, rowptr, col, (long)N, num_heads, scale, sd, y, lse, y_raw, ld);
-  return acheck(who);
+  return check_launch(who);
 }
 
 static int attn_bwd_any(int b16, const float* q, const void* k, const void* v, const float* y, const float* lse, const float* dy,
@@ -539,15 +527,15 @@ static int attn_bwd_any(int b16, const float* q, const void* k, const void* v, c
                         int64_t E, int H, int num_heads, float* dq, float* dk, float* dv, float* ws, size_t ws_bytes, AttnLd ld, void* stream,
                         const char* who) {
   if (!attn_args_ok(N, H, num_heads) || E < 0) {
-    snprintf(g_aerr, sizeof(g_aerr), "%s: bad arguments", who);
+    snprintf(g_err, sizeof(g_err), "%s: bad arguments", who);
     return 1;
   }
   if (ws_bytes < (size_t)2 * E * num_heads * sizeof(float)) {
-    snprintf(g_aerr, sizeof(g_aerr), "%s: workspace too small (2 * E * num_heads floats)", who);
+    snprintf(g_err, sizeof(g_err), "%s: workspace too small (2 * E * num_heads floats)", who);
     return 1;
   }
   if (!attn_ld_ok(ld, H, true)) {
-    snprintf(g_aerr, sizeof(g_aerr), "%s: row pitches must be multiples of 4 elements and >= hidden", who);
+    snprintf(g_err, sizeof(g_err), "%s: row pitches must be multiples of 4 elements and >= hidden", who);
     return 1;
   }
   if (N == 0) return 0;
@@ -572,7 +560,7 @@ static int attn_bwd_any(int b16, const float* q, const void* k, const void* v, c
   else if (b16 == 2) ATTN_BWD_GO(2);
   else ATTN_BWD_GO(0);
 #undef ATTN_BWD_GO
-  return acheck(who);
+  return check_launch(who);
 }
 
 extern "C" int mgn_sparse_attn_fwd(const float* q, const float* k, const float* v, const int32_t* rowptr, const int32_t* col, int64_t N, int H,
@@ -609,7 +597,7 @@ extern "C" int mgn_sparse_attn_fwd_s(const float* q, int64_t ldq, const void* k,
                                      const int32_t* rowptr, const int32_t* col, int64_t N, int H, int num_heads, float* y, float* lse,
                                      float* y_raw, void* stream) {
   const AttnLd ld{(int)ldq, (int)ldk, (int)ldv, H, H, H};
-  if (kv_bf16 < 0 || kv_bf16 > 2) return afail(1, "mgn_sparse_attn_fwd_s: kv_bf16 must be 0, 1 or 2");
+  if (kv_bf16 < 0 || kv_bf16 > 2) return fail(1, "mgn_sparse_attn_fwd_s: kv_bf16 must be 0, 1 or 2");
   return attn_fwd_any(kv_bf16, q, k, v, rowptr, col, N, H, num_heads, y, lse, y_raw, ld, stream, "mgn_sparse_attn_fwd_s");
 }
 
@@ -619,19 +607,19 @@ extern "C" int mgn_sparse_attn_bwd_s(const float* q, int64_t ldq, const void* k,
                                      int num_heads, float* dq, int64_t lddq, float* dk, int64_t lddk, float* dv, int64_t lddv, float* ws,
                                      size_t ws_bytes, void* stream) {
   const AttnLd ld{(int)ldq, (int)ldk, (int)ldv, (int)lddq, (int)lddk, (int)lddv};
-  if (kv_bf16 < 0 || kv_bf16 > 2) return afail(1, "mgn_sparse_attn_bwd_s: kv_bf16 must be 0, 1 or 2");
+  if (kv_bf16 < 0 || kv_bf16 > 2) return fail(1, "mgn_sparse_attn_bwd_s: kv_bf16 must be 0, 1 or 2");
   return attn_bwd_any(kv_bf16, q, k, v, y, lse, dy, rowptr, col, cptr, cperm, crow, N, E, H, num_heads, dq, dk, dv, ws, ws_bytes, ld,
                       stream, "mgn_sparse_attn_bwd_s");
 }
 
 extern "C" int mgn_sparse_attn_weights(const float* q, const float* k, const float* lse, const int32_t* rowptr, const int32_t* col,
                                        const int32_t* out_pos, int64_t N, int H, int num_heads, float* attn, void* stream) {
-  if (!attn_args_ok(N, H, num_heads) || lse == nullptr || attn == nullptr) return afail(1, "mgn_sparse_attn_weights: bad arguments");
+  if (!attn_args_ok(N, H, num_heads) || lse == nullptr || attn == nullptr) return fail(1, "mgn_sparse_attn_weights: bad arguments");
   if (N == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
   const float scale = 1.0f / sqrtf((float)(H / num_heads));
   ATTN_DISPATCH(k_attn_weights, 0, q, k, lse, rowptr, col, out_pos, (long)N, num_heads, scale, attn);
-  return acheck("mgn_sparse_attn_weights");
+  return check_launch("mgn_sparse_attn_weights");
 }
 
 // =====================================================================================================================
@@ -800,25 +788,25 @@ static int hax_args_ok(int64_t N, int H, int NH) {
 extern "C" int mgn_head_axis_attn_fwd(const float* q, const float* k, const float* v, int64_t N, int H, int num_heads, float* y,
                                       float* lse, void* stream) {
   if (!hax_args_ok(N, H, num_heads) || (N > 0 && (!q || !k || !v || !y || !lse)))
-    return afail(1, "mgn_head_axis_attn_fwd: num_heads must be 1/2/4/8/16 and divide hidden, hidden / num_heads <= 128");
+    return fail(1, "mgn_head_axis_attn_fwd: num_heads must be 1/2/4/8/16 and divide hidden, hidden / num_heads <= 128");
   if (N == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
   const int d = H / num_heads, nb = HAX_THREADS / d;
   const unsigned grid = (unsigned)((N + nb - 1) / nb);
   const size_t lds = (size_t)2 * nb * H * sizeof(float);
   HAX_LAUNCH(k_head_axis_attn_fwd, lds, q, k, v, (long)N, d, sqrtf((float)d), y, lse);
-  return acheck("mgn_head_axis_attn_fwd");
+  return check_launch("mgn_head_axis_attn_fwd");
 }
 
 extern "C" int mgn_head_axis_attn_bwd(const float* q, const float* k, const float* v, const float* y, const float* lse, const float* dy,
                                       int64_t N, int H, int num_heads, float* dq, float* dk, float* dv, void* stream) {
   if (!hax_args_ok(N, H, num_heads) || (N > 0 && (!q || !k || !v || !y || !lse || !dy || !dq || !dk || !dv)))
-    return afail(1, "mgn_head_axis_attn_bwd: num_heads must be 1/2/4/8/16 and divide hidden, hidden / num_heads <= 128");
+    return fail(1, "mgn_head_axis_attn_bwd: num_heads must be 1/2/4/8/16 and divide hidden, hidden / num_heads <= 128");
   if (N == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
   const int d = H / num_heads, nb = HAX_THREADS / d;
   const unsigned grid = (unsigned)((N + nb - 1) / nb);
   const size_t lds = ((size_t)4 * nb * H + 2 * nb * d) * sizeof(float);
   HAX_LAUNCH(k_head_axis_attn_bwd, lds, q, k, v, y, lse, dy, (long)N, d, sqrtf((float)d), dq, dk, dv);
-  return acheck("mgn_head_axis_attn_bwd");
+  return check_launch("mgn_head_axis_attn_bwd");
 }

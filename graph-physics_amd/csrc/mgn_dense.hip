@@ -28,20 +28,8 @@ typedef __bf16 bf16x8_d __attribute__((ext_vector_type(8)));
 #define MFMA_BF16(a, b, c) \
   __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_d, (a)), __builtin_bit_cast(bf16x8_d, (b)), (c), 0, 0, 0)
 
-static thread_local char g_derr[256] = "";
-extern "C" const char* mgn_dense_last_error(void) { return g_derr; }
-static int dfail(int code, const char* msg) {
-  snprintf(g_derr, sizeof(g_derr), "%s", msg);
-  return code;
-}
-static int dcheck(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    snprintf(g_derr, sizeof(g_derr), "%s: %s", what, hipGetErrorString(e));
-    return 2;
-  }
-  return 0;
-}
+#include "mgn_host.inc"  // g_err, fail, check_launch
+extern "C" const char* mgn_dense_last_error(void) { return g_err; }
 
 // round to nearest-even bf16, returned as fp32 (v_cvt_pk_bf16_f32: the hardware conversion)
 typedef float f32x2_d __attribute__((ext_vector_type(2)));
@@ -633,41 +621,41 @@ static int launch_linear(const mgn_linear_args& a, hipStream_t s) {
 
 extern "C" int mgn_linear_fwd(const mgn_linear_args* args, void* stream) {
   const mgn_linear_args& a = *args;
-  if (a.M < 0 || a.x == nullptr || a.W == nullptr || a.out == nullptr) return dfail(1, "mgn_linear_fwd: missing operand");
+  if (a.M < 0 || a.x == nullptr || a.W == nullptr || a.out == nullptr) return fail(1, "mgn_linear_fwd: missing operand");
   const int K = a.K1 + a.K2 + a.K3;
   if (a.K1 < 16 || (a.K1 & 15) || a.K2 < 0 || (a.K2 & 15) || a.K3 < 0 || (a.K3 & 15) || K > 384 || (a.K2 > 0 && a.x2 == nullptr) ||
       (a.K3 > 0 && (a.x3 == nullptr || a.K2 == 0)))
-    return dfail(1, "mgn_linear_fwd: input widths must be multiples of 16, at most 384 together");
-  if (a.K3 > 0 && (a.ldx3 < a.K3 || (a.ldx3 & 3))) return dfail(1, "mgn_linear_fwd: bad leading dimension of the third phase");
-  if (a.N < 16 || (a.N & 15) || a.N > 1024) return dfail(1, "mgn_linear_fwd: output width must be a multiple of 16");
+    return fail(1, "mgn_linear_fwd: input widths must be multiples of 16, at most 384 together");
+  if (a.K3 > 0 && (a.ldx3 < a.K3 || (a.ldx3 & 3))) return fail(1, "mgn_linear_fwd: bad leading dimension of the third phase");
+  if (a.N < 16 || (a.N & 15) || a.N > 1024) return fail(1, "mgn_linear_fwd: output width must be a multiple of 16");
   if (a.ldx < a.K1 || (a.ldx & 3) || (a.K2 > 0 && (a.ldx2 < a.K2 || (a.ldx2 & 3))) || a.ldw < (a.w_transposed ? a.N : K) || (a.ldw & 3) || a.ldo < a.N || (a.ldo & 3) ||
       (a.resid != nullptr && (a.ldr < a.N || (a.ldr & 3))))
-    return dfail(1, "mgn_linear_fwd: leading dimensions must cover the widths and keep rows 16-byte aligned");
-  if (a.act < -1 || a.act > MGN_ACT_GELU) return dfail(1, "mgn_linear_fwd: act must be MGN_ACT_NONE, _RELU, _SILU or _GELU");
+    return fail(1, "mgn_linear_fwd: leading dimensions must cover the widths and keep rows 16-byte aligned");
+  if (a.act < -1 || a.act > MGN_ACT_GELU) return fail(1, "mgn_linear_fwd: act must be MGN_ACT_NONE, _RELU, _SILU or _GELU");
   if (a.norm_scale_outer != nullptr && (a.norm_scale == nullptr || a.K2 > 0 || a.idx != nullptr))
-    return dfail(1, "mgn_linear_fwd: norm_scale_outer needs norm_scale and a single ungathered input phase");
-  if ((a.z16 || a.x16 || a.out16) && a.precision != 1) return dfail(1, "mgn_linear_fwd: two-byte rows (z16 / x16 / out16) need precision 1");
+    return fail(1, "mgn_linear_fwd: norm_scale_outer needs norm_scale and a single ungathered input phase");
+  if ((a.z16 || a.x16 || a.out16) && a.precision != 1) return fail(1, "mgn_linear_fwd: two-byte rows (z16 / x16 / out16) need precision 1");
   if (a.x16 && (a.norm_scale != nullptr || a.K2 > 0 || a.idx != nullptr || a.W2 != nullptr))
-    return dfail(1, "mgn_linear_fwd: x16 takes one ungathered input phase without a norm prologue or a gated product");
-  if (a.out16 && a.resid != nullptr) return dfail(1, "mgn_linear_fwd: out16 has no residual epilogue");
+    return fail(1, "mgn_linear_fwd: x16 takes one ungathered input phase without a norm prologue or a gated product");
+  if (a.out16 && a.resid != nullptr) return fail(1, "mgn_linear_fwd: out16 has no residual epilogue");
   if (a.gb_z1 != nullptr && (a.gb_z2 == nullptr || a.out2 == nullptr || a.W2 != nullptr || a.b != nullptr || a.resid != nullptr || a.saveZ1 != nullptr ||
                              a.ldo != a.N))
-    return dfail(1, "mgn_linear_fwd: the gated-backward epilogue takes gb_z1, gb_z2, out2, dense outputs, no W2 / bias / residual / saves");
-  if (a.precision != 0 && a.precision != 1) return dfail(1, "mgn_linear_fwd: precision must be 0 or 1");
+    return fail(1, "mgn_linear_fwd: the gated-backward epilogue takes gb_z1, gb_z2, out2, dense outputs, no W2 / bias / residual / saves");
+  if (a.precision != 0 && a.precision != 1) return fail(1, "mgn_linear_fwd: precision must be 0 or 1");
   if (a.M == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
   switch (K >> 4) {
 #define LIN_CASE(KB_)                                                                                                                \
   case KB_: {                                                                                                                        \
     const int rc_ = launch_linear<KB_>(a, s);                                                                                        \
-    if (rc_ == 3) return dfail(1, "mgn_linear_fwd: a transposed weight / the gated-backward epilogue / an outer norm need the LDS-staged form (mgn_linear_accepts_transposed)");  \
-    if (rc_) return dfail(2, "mgn_linear_fwd: cannot reserve LDS");                                                                  \
+    if (rc_ == 3) return fail(1, "mgn_linear_fwd: a transposed weight / the gated-backward epilogue / an outer norm need the LDS-staged form (mgn_linear_accepts_transposed)");  \
+    if (rc_) return fail(2, "mgn_linear_fwd: cannot reserve LDS");                                                                  \
   } break;
     LIN_CASE(1) LIN_CASE(2) LIN_CASE(3) LIN_CASE(4) LIN_CASE(6) LIN_CASE(8) LIN_CASE(12) LIN_CASE(16) LIN_CASE(24)
 #undef LIN_CASE
-    default: return dfail(1, "mgn_linear_fwd: total input width must be 16, 32, 48, 64, 96, 128, 192, 256 or 384");
+    default: return fail(1, "mgn_linear_fwd: total input width must be 16, 32, 48, 64, 96, 128, 192, 256 or 384");
   }
-  return dcheck("mgn_linear_fwd");
+  return check_launch("mgn_linear_fwd");
 }
 
 // ------------------------------------------------------------------ activation / gated-product backward
@@ -696,11 +684,11 @@ extern "C" int mgn_act_gate_bwd(const float* dP, const float* Z1, const float* Z
                                 float* dZ2, void* stream) {
   if (M < 0 || N < 4 || (N & 3) || dP == nullptr || Z1 == nullptr || dZ1 == nullptr || (Z2 != nullptr && dZ2 == nullptr) || act < -1 ||
       act > MGN_ACT_GELU)
-    return dfail(1, "mgn_act_gate_bwd: bad arguments");
+    return fail(1, "mgn_act_gate_bwd: bad arguments");
   const long n4 = (long)M * N / 4;
   if (n4 == 0) return 0;
   hipLaunchKernelGGL(k_act_gate_bwd, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dP, Z1, Z2, n4, act, precision, dZ1, dZ2);
-  return dcheck("mgn_act_gate_bwd");
+  return check_launch("mgn_act_gate_bwd");
 }
 
 // ------------------------------------------------------------------ stand-alone RMSNorm (layers.py:73-129)
@@ -731,7 +719,7 @@ __global__ void __launch_bounds__(256) k_rownorm_fwd(const float* __restrict__ x
   }
 }
 extern "C" int mgn_rownorm_fwd(const float* x, int ldx, int K, const float* scale, float eps, int64_t M, float* y, float* inv_out, void* stream) {
-  if (M < 0 || x == nullptr || scale == nullptr || y == nullptr || K < 1 || K > 384 || ldx < K) return dfail(1, "mgn_rownorm_fwd: bad arguments (at most 384 columns)");
+  if (M < 0 || x == nullptr || scale == nullptr || y == nullptr || K < 1 || K > 384 || ldx < K) return fail(1, "mgn_rownorm_fwd: bad arguments (at most 384 columns)");
   if (M == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
   unsigned grid = (unsigned)((M + 3) / 4);
@@ -740,9 +728,9 @@ extern "C" int mgn_rownorm_fwd(const float* x, int ldx, int K, const float* scal
 #define RF_CASE(P_) case P_: hipLaunchKernelGGL(k_rownorm_fwd<P_>, dim3(grid), dim3(256), 0, s, x, ldx, K, scale, eps, (long)M, y, inv_out); break;
     RF_CASE(1) RF_CASE(2) RF_CASE(3) RF_CASE(4) RF_CASE(5) RF_CASE(6)
 #undef RF_CASE
-    default: return dfail(1, "mgn_rownorm_fwd: width out of range");
+    default: return fail(1, "mgn_rownorm_fwd: width out of range");
   }
-  return dcheck("mgn_rownorm_fwd");
+  return check_launch("mgn_rownorm_fwd");
 }
 
 // ------------------------------------------------------------------ RMSNorm-prologue backward
@@ -917,13 +905,13 @@ extern "C" size_t mgn_rownorm_bwd_workspace_bytes(int K) { return (size_t)(RN_GR
 extern "C" int mgn_rownorm_bwd(const float* dn, const mgn_rownorm_phase* phases, int nphase, const float* inv, const float* scale, float eps,
                                int64_t M, float* dscale, void* ws, size_t ws_bytes, void* stream) {
   if (M < 0 || dn == nullptr || phases == nullptr || nphase < 1 || nphase > 3 || inv == nullptr || scale == nullptr || dscale == nullptr)
-    return dfail(1, "mgn_rownorm_bwd: bad arguments");
+    return fail(1, "mgn_rownorm_bwd: bad arguments");
   RnPhases P;
   int K = 0;
   for (int p = 0; p < 3; ++p) {
     const bool on = p < nphase;
     if (on && (phases[p].x == nullptr || phases[p].dx == nullptr || phases[p].K < 1 || phases[p].ldx < phases[p].K || phases[p].lddx < phases[p].K))
-      return dfail(1, "mgn_rownorm_bwd: bad phase");
+      return fail(1, "mgn_rownorm_bwd: bad phase");
     P.x[p] = on ? phases[p].x : phases[0].x;
     P.idx[p] = on ? phases[p].idx : nullptr;
     P.ld[p] = on ? phases[p].ldx : 0;
@@ -935,8 +923,8 @@ extern "C" int mgn_rownorm_bwd(const float* dn, const mgn_rownorm_phase* phases,
   }
   P.k0[3] = K;
   for (int p = nphase; p < 3; ++p) P.k0[p] = K;
-  if (K > 384) return dfail(1, "mgn_rownorm_bwd: at most 384 columns");
-  if (ws == nullptr || ws_bytes < mgn_rownorm_bwd_workspace_bytes(K)) return dfail(1, "mgn_rownorm_bwd: workspace too small");
+  if (K > 384) return fail(1, "mgn_rownorm_bwd: at most 384 columns");
+  if (ws == nullptr || ws_bytes < mgn_rownorm_bwd_workspace_bytes(K)) return fail(1, "mgn_rownorm_bwd: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   unsigned grid = (unsigned)((M + 15) / 16);   // >= 4 rows per wave: enough loads in flight per wave, enough waves per CU
   if (grid > RN_GRID) grid = RN_GRID;
@@ -946,7 +934,7 @@ extern "C" int mgn_rownorm_bwd(const float* dn, const mgn_rownorm_phase* phases,
 #define RN_CASE(P_) case P_: hipLaunchKernelGGL(k_rownorm_bwd<P_>, dim3(grid), dim3(256), 0, s, dn, P, K, inv, scale, eps, (long)M, part); break;
     RN_CASE(1) RN_CASE(2) RN_CASE(3) RN_CASE(4) RN_CASE(5) RN_CASE(6)
 #undef RN_CASE
-    default: return dfail(1, "mgn_rownorm_bwd: width out of range");
+    default: return fail(1, "mgn_rownorm_bwd: width out of range");
   }
   const unsigned kb_ = (unsigned)((K + 63) / 64);
   if (grid > RN_CHUNK) {
@@ -957,7 +945,7 @@ extern "C" int mgn_rownorm_bwd(const float* dn, const mgn_rownorm_phase* phases,
   } else {
     hipLaunchKernelGGL(k_colsum_parts, dim3(kb_, 1), dim3(256), 0, s, (const float*)part, (int)grid, (int)grid, K, dscale);
   }
-  return dcheck("mgn_rownorm_bwd");
+  return check_launch("mgn_rownorm_bwd");
 }
 
 extern "C" int mgn_rownorm2_bwd(const float* dn, const float* x, int ldx, int K, const float* inv_outer, const float* scale_outer,
@@ -965,8 +953,8 @@ extern "C" int mgn_rownorm2_bwd(const float* dn, const float* x, int ldx, int K,
                                 float* dscale_io, void* ws, size_t ws_bytes, void* stream) {
   if (M < 0 || dn == nullptr || x == nullptr || inv_outer == nullptr || scale_outer == nullptr || inv_inner == nullptr || scale_inner == nullptr ||
       dx == nullptr || dscale_io == nullptr || K < 1 || K > 192 || ldx < K)
-    return dfail(1, "mgn_rownorm2_bwd: bad arguments (at most 192 columns)");
-  if (ws == nullptr || ws_bytes < mgn_rownorm_bwd_workspace_bytes(2 * K)) return dfail(1, "mgn_rownorm2_bwd: workspace too small");
+    return fail(1, "mgn_rownorm2_bwd: bad arguments (at most 192 columns)");
+  if (ws == nullptr || ws_bytes < mgn_rownorm_bwd_workspace_bytes(2 * K)) return fail(1, "mgn_rownorm2_bwd: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   unsigned grid = (unsigned)((M + 15) / 16);
   if (grid > RN_GRID) grid = RN_GRID;
@@ -975,14 +963,14 @@ extern "C" int mgn_rownorm2_bwd(const float* dn, const float* x, int ldx, int K,
   float* both = dscale_io;   // [ds_inner | ds_outer]
   if (M == 0) {
     hipMemsetAsync(dscale_io, 0, (size_t)2 * K * sizeof(float), s);
-    return dcheck("mgn_rownorm2_bwd");
+    return check_launch("mgn_rownorm2_bwd");
   }
   switch ((K + 63) / 64) {
 #define RN2_CASE(P_) \
   case P_: hipLaunchKernelGGL(k_rownorm2_bwd<P_>, dim3(grid), dim3(256), 0, s, dn, x, ldx, K, inv_outer, scale_outer, inv_inner, scale_inner, eps, (long)M, acc, dx, part); break;
     RN2_CASE(1) RN2_CASE(2) RN2_CASE(3)
 #undef RN2_CASE
-    default: return dfail(1, "mgn_rownorm2_bwd: width out of range");
+    default: return fail(1, "mgn_rownorm2_bwd: width out of range");
   }
   const int K2 = 2 * K;
   const unsigned kb_ = (unsigned)((K2 + 63) / 64);
@@ -994,5 +982,5 @@ extern "C" int mgn_rownorm2_bwd(const float* dn, const float* x, int ldx, int K,
   } else {
     hipLaunchKernelGGL(k_colsum_parts, dim3(kb_, 1), dim3(256), 0, s, (const float*)part, (int)grid, (int)grid, K2, both);
   }
-  return dcheck("mgn_rownorm2_bwd");
+  return check_launch("mgn_rownorm2_bwd");
 }

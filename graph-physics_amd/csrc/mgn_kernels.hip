@@ -2103,19 +2103,7 @@ __global__ void __launch_bounds__(256) k_csr_sortbig(const int32_t* __restrict__
 }
 
 // ============================================================================ C ABI
-static thread_local char g_err[256] = "";
-static int fail(int code, const char* msg) {
-  snprintf(g_err, sizeof(g_err), "%s", msg);
-  return code;
-}
-static int check_launch(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e));
-    return 2;
-  }
-  return 0;
-}
+#include "mgn_host.inc"  // g_err, fail, check_launch
 
 struct MlpPlan {
   bool lds;       // LDS-weight kernel (H = 128, full widths)

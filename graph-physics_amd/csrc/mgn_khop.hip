@@ -13,22 +13,13 @@
 //             ordered scan with prefix popcounts.  KH_BATCH rows are in flight at a time (a persistent grid), so the
 //             workspace is bounded.  Exact but slow: ~3 * N/32 words per level per row.
 // No global atomics on the fill path of either kind: the output is bit-identical run to run.
-#include <hip/hip_runtime.h>
-#include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
-#include <rocprim/device/device_select.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
-#include <stdint.h>
-#include <stdio.h>
-#include <string.h>
 #include "mgn_hip.h"
+#include "mgn_host.inc"       // g_err, fail, check_launch, workspace carving, count -> fill header
+#include "mgn_graphprim.inc"  // edge keys, sort_unique_keys
 
-static thread_local char g_kerr[256] = "";
-extern "C" const char* mgn_khop_last_error(void) { return g_kerr; }
-static int kfail(int code, const char* msg) {
-  snprintf(g_kerr, sizeof(g_kerr), "%s", msg);
-  return code;
-}
+extern "C" const char* mgn_khop_last_error(void) { return g_err; }
 
 #define KH_CAP 1024            // ids one row may hold on the LDS path (a power of two: the bitonic sort pads to it)
 #define KH_SLOTS (2 * KH_CAP)  // hash slots per row: the set stays at most half full, so probing ends
@@ -39,28 +30,12 @@ static int kfail(int code, const char* msg) {
 #define KH_MAGIC 0x6b686f70313336ull
 
 // ---------------------------------------------------------------------------------------- prep: edge list -> CSR
-// invalid index -> err flag; self loops carry nothing (the origin never appears in its own row): both get the all-ones
-// key, which sorts last and collapses into one trailing entry.
-__global__ void __launch_bounds__(256) k_khop_keys(const int64_t* __restrict__ r0, const int64_t* __restrict__ r1, long E, long N,
-                                                   uint64_t* __restrict__ keys, int* __restrict__ err) {
-  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= E) return;
-  const int64_t a = r0[e], b = r1[e];
-  const bool ok = a >= 0 && a < N && b >= 0 && b < N;
-  if (!ok) *err = 1;
-  keys[e] = (ok && a != b) ? (uint64_t)a * (uint64_t)N + (uint64_t)b : ~0ull;
-}
-
-__device__ __forceinline__ size_t khop_nnz(const uint64_t* __restrict__ uniq, const size_t* __restrict__ n_uniq) {
-  size_t n = *n_uniq;
-  if (n > 0 && uniq[n - 1] == ~0ull) --n;
-  return n;
-}
-
+// keys by k_edge_list_keys<false>: one direction, and self loops are dropped -- they carry nothing (the origin never appears
+// in its own row).
 __global__ void __launch_bounds__(256) k_khop_col(const uint64_t* __restrict__ uniq, const size_t* __restrict__ n_uniq, long N, long E,
                                                   int32_t* __restrict__ col) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= E || (size_t)i >= khop_nnz(uniq, n_uniq)) return;
+  if (i >= E || (size_t)i >= edge_key_count(uniq, n_uniq)) return;
   col[i] = (int32_t)(uniq[i] % (uint64_t)N);
 }
 
@@ -69,7 +44,7 @@ __global__ void __launch_bounds__(256) k_khop_rowptr(const uint64_t* __restrict_
                                                      int64_t* __restrict__ rowptr) {
   const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (r > N) return;
-  const size_t n = khop_nnz(uniq, n_uniq);
+  const size_t n = edge_key_count(uniq, n_uniq);
   const uint64_t want = (uint64_t)r * (uint64_t)N;
   size_t lo = 0, hi = n;
   while (lo < hi) {
@@ -307,30 +282,26 @@ struct KhopPlan {
 };
 static KhopPlan khop_plan(int64_t N, int64_t E) {
   KhopPlan p;
+  WsCarver c;
   const size_t n = (size_t)E, rows = (size_t)N;
-  size_t t1 = 0, t2 = 0, t3 = 0, t4 = 0;
-  (void)rocprim::radix_sort_keys(nullptr, t1, (uint64_t*)nullptr, (uint64_t*)nullptr, n, 0, 64, (hipStream_t)0);
-  (void)rocprim::unique(nullptr, t2, (uint64_t*)nullptr, (uint64_t*)nullptr, (size_t*)nullptr, n, rocprim::equal_to<uint64_t>(), (hipStream_t)0);
+  size_t t3 = 0, t4 = 0;  // the temporary block serves sort + unique, select and scan in turn
   (void)rocprim::select(nullptr, t3, rocprim::counting_iterator<int32_t>(0), (int32_t*)nullptr, (size_t*)nullptr, rows, IsOverflow{nullptr}, (hipStream_t)0);
   (void)rocprim::exclusive_scan(nullptr, t4, (int64_t*)nullptr, (int64_t*)nullptr, (int64_t)0, rows + 1, rocprim::plus<int64_t>(), (hipStream_t)0);
-  size_t t = t1 > t2 ? t1 : t2;
-  t = t > t3 ? t : t3;
-  t = t > t4 ? t : t4;
-  p.tmp_bytes = t + 256;
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  p.header = 0;
-  p.keys = 256;
-  p.sorted = al(p.keys + n * 8);
-  p.uniq = al(p.sorted + n * 8);
-  p.flags = al(p.uniq + n * 8);                 // [0] unique count (size_t), [1] overflow rows (size_t), [2] err (int)
-  p.rowptr = p.flags + 256;
-  p.col = al(p.rowptr + (rows + 1) * 8);
-  p.cnt = al(p.col + n * 4);
-  p.offs = al(p.cnt + (rows + 1) * 8);
-  p.ovf = al(p.offs + (rows + 1) * 8);
-  p.bitmaps = al(p.ovf + rows * 4);
-  p.tmp = al(p.bitmaps + (size_t)KH_BATCH * 3 * ((rows + 31) / 32) * 4);
-  p.total = p.tmp + p.tmp_bytes;
+  const size_t t = (t3 > t4 ? t3 : t4) + 256, tsu = sort_unique_tmp_bytes(n);
+  p.tmp_bytes = t > tsu ? t : tsu;
+  p.header = c.take(256);
+  p.keys = c.take(n * 8);
+  p.sorted = c.take(n * 8);
+  p.uniq = c.take(n * 8);
+  p.flags = c.take(256);  // [0] unique count (size_t), [1] overflow rows (size_t), [2] err (int)
+  p.rowptr = c.take((rows + 1) * 8);
+  p.col = c.take(n * 4);
+  p.cnt = c.take((rows + 1) * 8);
+  p.offs = c.take((rows + 1) * 8);
+  p.ovf = c.take(rows * 4);
+  p.bitmaps = c.take((size_t)KH_BATCH * 3 * ((rows + 31) / 32) * 4);
+  p.tmp = c.take(p.tmp_bytes);
+  p.total = c.end;
   return p;
 }
 
@@ -341,26 +312,16 @@ extern "C" size_t mgn_khop_workspace_bytes(int64_t N, int64_t E) {
   return khop_plan(N, E).total + 256;
 }
 
-static int khop_check(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    snprintf(g_kerr, sizeof(g_kerr), "%s: %s", what, hipGetErrorString(e));
-    return 2;
-  }
-  return 0;
-}
-
 extern "C" int mgn_khop_count(const int64_t* row0, const int64_t* row1, int64_t E, int64_t N, int hops, int64_t* n_out_host,
                               int64_t* n_overflow_rows_host, void* ws, size_t ws_bytes, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (hops < 2) return kfail(1, "mgn_khop_count: hops must be >= 2 (one hop is the input itself)");
-  if (N < 1 || N > KH_NMAX) return kfail(1, "mgn_khop_count: N must be in [1, 2^31 - 2] (32-bit node ids, all-ones is the empty slot)");
-  if (E < 0) return kfail(1, "mgn_khop_count: E must be >= 0");
-  if (!n_out_host || !n_overflow_rows_host) return kfail(1, "mgn_khop_count: n_out_host / n_overflow_rows_host must not be null");
+  if (hops < 2) return fail(1, "mgn_khop_count: hops must be >= 2 (one hop is the input itself)");
+  if (N < 1 || N > KH_NMAX) return fail(1, "mgn_khop_count: N must be in [1, 2^31 - 2] (32-bit node ids, all-ones is the empty slot)");
+  if (E < 0) return fail(1, "mgn_khop_count: E must be >= 0");
+  if (!n_out_host || !n_overflow_rows_host) return fail(1, "mgn_khop_count: n_out_host / n_overflow_rows_host must not be null");
   const KhopPlan p = khop_plan(N, E);
-  const size_t base = ((size_t)ws + 255) & ~(size_t)255;
-  if (!ws || ws_bytes < (base - (size_t)ws) + p.total) return kfail(1, "mgn_khop_count: workspace (ws_bytes) too small: see mgn_khop_workspace_bytes");
-  char* w = (char*)base;
+  char* w = ws_base(ws, ws_bytes, p.total);
+  if (!w) return fail(1, "mgn_khop_count: workspace (ws_bytes) too small: see mgn_khop_workspace_bytes");
   uint64_t *keys = (uint64_t*)(w + p.keys), *sorted = (uint64_t*)(w + p.sorted), *uniq = (uint64_t*)(w + p.uniq);
   size_t* n_uniq = (size_t*)(w + p.flags);
   size_t* n_ovf = n_uniq + 1;
@@ -373,42 +334,37 @@ extern "C" int mgn_khop_count(const int64_t* row0, const int64_t* row1, int64_t 
   h.magic = KH_MAGIC; h.N = N; h.E = E; h.hops = hops;
   *n_out_host = 0;
   *n_overflow_rows_host = 0;
-  if (hipMemsetAsync(w + p.header, 0, 256, s) != hipSuccess) return kfail(2, "mgn_khop_count: memset");  // no stale header on failure
-  if (hipMemsetAsync(w + p.flags, 0, 256, s) != hipSuccess) return kfail(2, "mgn_khop_count: memset");
+  if (int rc = ws_header_clear(w + p.header, 256, s, "mgn_khop_count")) return rc;
+  if (hipMemsetAsync(w + p.flags, 0, 256, s) != hipSuccess) return fail(2, "mgn_khop_count: memset");
   if (E > 0) {
-    hipLaunchKernelGGL(k_khop_keys, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, s, row0, row1, (long)E, (long)N, keys, err);
-    size_t tb = p.tmp_bytes;
-    if (rocprim::radix_sort_keys(w + p.tmp, tb, keys, sorted, (size_t)E, 0, 64, s) != hipSuccess) return kfail(2, "mgn_khop_count: sort");
-    tb = p.tmp_bytes;
-    if (rocprim::unique(w + p.tmp, tb, sorted, uniq, n_uniq, (size_t)E, rocprim::equal_to<uint64_t>(), s) != hipSuccess)
-      return kfail(2, "mgn_khop_count: unique");
+    hipLaunchKernelGGL(k_edge_list_keys<false>, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, s, row0, row1, (long)E, (long)N, keys, err);
+    if (int rc = sort_unique_keys(w + p.tmp, p.tmp_bytes, keys, sorted, uniq, n_uniq, (size_t)E, s, "mgn_khop_count")) return rc;
     hipLaunchKernelGGL(k_khop_col, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, s, uniq, n_uniq, (long)N, (long)E, col);
   }
   // with E == 0 the unique count stays 0 and every rowptr entry is 0
   hipLaunchKernelGGL(k_khop_rowptr, dim3((unsigned)((N + 1 + 255) / 256)), dim3(256), 0, s, uniq, n_uniq, (long)N, rowptr);
-  if (hipMemsetAsync(cnt + N, 0, sizeof(int64_t), s) != hipSuccess) return kfail(2, "mgn_khop_count: memset");
+  if (hipMemsetAsync(cnt + N, 0, sizeof(int64_t), s) != hipSuccess) return fail(2, "mgn_khop_count: memset");
   const unsigned row_grid = (unsigned)((N + KH_WAVES - 1) / KH_WAVES);
   hipLaunchKernelGGL(k_khop_rows<false>, dim3(row_grid), dim3(64 * KH_WAVES), 0, s, rowptr, col, (long)N, hops, cnt, (const int64_t*)nullptr,
                      (int64_t*)nullptr, (int64_t*)nullptr);
   size_t tb = p.tmp_bytes;
   if (rocprim::select(w + p.tmp, tb, rocprim::counting_iterator<int32_t>(0), ovf, n_ovf, (size_t)N, IsOverflow{cnt}, s) != hipSuccess)
-    return kfail(2, "mgn_khop_count: select");
+    return fail(2, "mgn_khop_count: select");
   hipLaunchKernelGGL(k_khop_overflow<false>, dim3(KH_BATCH), dim3(256), 0, s, rowptr, col, (long)N, hops, ovf, n_ovf, bitmaps, cnt,
                      (const int64_t*)nullptr, (int64_t*)nullptr, (int64_t*)nullptr);
   tb = p.tmp_bytes;
   if (rocprim::exclusive_scan(w + p.tmp, tb, cnt, offs, (int64_t)0, (size_t)N + 1, rocprim::plus<int64_t>(), s) != hipSuccess)
-    return kfail(2, "mgn_khop_count: scan");
-  if (int rc = khop_check("mgn_khop_count")) return rc;
+    return fail(2, "mgn_khop_count: scan");
+  if (int rc = check_launch("mgn_khop_count")) return rc;
   int64_t total = 0;
   unsigned long long flags[3] = {0, 0, 0};
-  if (hipMemcpyAsync(&total, offs + N, sizeof(int64_t), hipMemcpyDeviceToHost, s) != hipSuccess) return kfail(2, "mgn_khop_count: memcpy");
-  if (hipMemcpyAsync(flags, w + p.flags, sizeof(flags), hipMemcpyDeviceToHost, s) != hipSuccess) return kfail(2, "mgn_khop_count: memcpy");
-  if (hipStreamSynchronize(s) != hipSuccess) return kfail(2, "mgn_khop_count: sync failed");
-  if (*(int*)&flags[2]) return kfail(3, "mgn_khop_count: edge index outside [0, N)");
+  if (hipMemcpyAsync(&total, offs + N, sizeof(int64_t), hipMemcpyDeviceToHost, s) != hipSuccess) return fail(2, "mgn_khop_count: memcpy");
+  if (hipMemcpyAsync(flags, w + p.flags, sizeof(flags), hipMemcpyDeviceToHost, s) != hipSuccess) return fail(2, "mgn_khop_count: memcpy");
+  if (hipStreamSynchronize(s) != hipSuccess) return fail(2, "mgn_khop_count: sync failed");
+  if (*(int*)&flags[2]) return fail(3, "mgn_khop_count: edge index outside [0, N)");
   h.n_out = total;
   h.n_overflow = (int64_t)flags[1];
-  if (hipMemcpyAsync(w + p.header, &h, sizeof(h), hipMemcpyHostToDevice, s) != hipSuccess) return kfail(2, "mgn_khop_count: memcpy");
-  if (hipStreamSynchronize(s) != hipSuccess) return kfail(2, "mgn_khop_count: sync failed");  // h is a stack variable
+  if (int rc = ws_header_put(w + p.header, &h, sizeof(h), s, "mgn_khop_count")) return rc;
   *n_out_host = total;
   *n_overflow_rows_host = h.n_overflow;
   return 0;
@@ -416,21 +372,19 @@ extern "C" int mgn_khop_count(const int64_t* row0, const int64_t* row1, int64_t 
 
 extern "C" int mgn_khop_fill(const void* ws, size_t ws_bytes, int64_t N, int hops, int64_t* out0, int64_t* out1, int64_t cap, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (hops < 2) return kfail(1, "mgn_khop_fill: hops must be >= 2");
-  if (N < 1 || N > KH_NMAX) return kfail(1, "mgn_khop_fill: N must be in [1, 2^31 - 2]");
-  if (!ws || ws_bytes < 512) return kfail(1, "mgn_khop_fill: workspace (ws_bytes) too small");
-  if (cap < 0) return kfail(1, "mgn_khop_fill: cap must be >= 0");
-  const size_t base = ((size_t)ws + 255) & ~(size_t)255;
-  char* w = (char*)base;
+  if (hops < 2) return fail(1, "mgn_khop_fill: hops must be >= 2");
+  if (N < 1 || N > KH_NMAX) return fail(1, "mgn_khop_fill: N must be in [1, 2^31 - 2]");
+  if (!ws || ws_bytes < 512) return fail(1, "mgn_khop_fill: workspace (ws_bytes) too small");
+  if (cap < 0) return fail(1, "mgn_khop_fill: cap must be >= 0");
+  char* w = (char*)align256((size_t)ws);  // the header fits: 255 + 256 < 512
   KhopHeader h;
-  if (hipMemcpyAsync(&h, w, sizeof(h), hipMemcpyDeviceToHost, s) != hipSuccess) return kfail(2, "mgn_khop_fill: memcpy");
-  if (hipStreamSynchronize(s) != hipSuccess) return kfail(2, "mgn_khop_fill: sync failed");
-  if (h.magic != KH_MAGIC || h.N != N || h.hops != hops) return kfail(1, "mgn_khop_fill: the workspace does not hold a mgn_khop_count of this N / hops");
+  if (int rc = ws_header_get(w, &h, sizeof(h), s, "mgn_khop_fill")) return rc;
+  if (h.magic != KH_MAGIC || h.N != N || h.hops != hops) return fail(1, "mgn_khop_fill: the workspace does not hold a mgn_khop_count of this N / hops");
   const KhopPlan p = khop_plan(N, h.E);
-  if (ws_bytes < (base - (size_t)ws) + p.total) return kfail(1, "mgn_khop_fill: workspace (ws_bytes) too small");
-  if (cap < h.n_out) return kfail(1, "mgn_khop_fill: cap is smaller than the counted number of pairs");
+  if (!ws_base(ws, ws_bytes, p.total)) return fail(1, "mgn_khop_fill: workspace (ws_bytes) too small");
+  if (cap < h.n_out) return fail(1, "mgn_khop_fill: cap is smaller than the counted number of pairs");
   if (h.n_out == 0) return 0;
-  if (!out0 || !out1) return kfail(1, "mgn_khop_fill: out0 / out1 must not be null");
+  if (!out0 || !out1) return fail(1, "mgn_khop_fill: out0 / out1 must not be null");
   const int64_t *rowptr = (const int64_t*)(w + p.rowptr), *offs = (const int64_t*)(w + p.offs);
   int64_t* cnt = (int64_t*)(w + p.cnt);
   const int32_t *col = (const int32_t*)(w + p.col), *ovf = (const int32_t*)(w + p.ovf);
@@ -440,5 +394,5 @@ extern "C" int mgn_khop_fill(const void* ws, size_t ws_bytes, int64_t N, int hop
   hipLaunchKernelGGL(k_khop_rows<true>, dim3(row_grid), dim3(64 * KH_WAVES), 0, s, rowptr, col, (long)N, hops, cnt, offs, out0, out1);
   if (h.n_overflow > 0)
     hipLaunchKernelGGL(k_khop_overflow<true>, dim3(KH_BATCH), dim3(256), 0, s, rowptr, col, (long)N, hops, ovf, n_ovf, bitmaps, cnt, offs, out0, out1);
-  return khop_check("mgn_khop_fill");
+  return check_launch("mgn_khop_fill");
 }

@@ -23,12 +23,8 @@
 #include <stdio.h>
 #include "mgn_hip.h"
 
-static thread_local char g_kerr[256] = "";
-extern "C" const char* mgn_knn_last_error(void) { return g_kerr; }
-static int kfail(int code, const char* msg) {
-  snprintf(g_kerr, sizeof(g_kerr), "%s", msg);
-  return code;
-}
+#include "mgn_host.inc"  // g_err, fail, check_launch
+extern "C" const char* mgn_knn_last_error(void) { return g_err; }
 
 #define KNN_THREADS 256
 #define KNN_TILE 1024  // reference points per LDS tile: 4 KiB per coordinate
@@ -191,15 +187,6 @@ __global__ void __launch_bounds__(256) k_knn_interp_bwd(const float* __restrict_
 }
 
 // ---------------------------------------------------------------------------------------- host side
-static int knn_check_launch(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    snprintf(g_kerr, sizeof(g_kerr), "%s: %s", what, hipGetErrorString(e));
-    return 2;
-  }
-  return 0;
-}
-
 static unsigned knn_grid(long items) {
   const long nb = (items + 255) / 256;
   return (unsigned)(nb < 1 ? 1 : (nb > 65536 ? 65536 : nb));  // grid-stride beyond
@@ -221,47 +208,47 @@ static void knn_launch(int k, dim3 grid, hipStream_t s, const float* x, const fl
 extern "C" int mgn_knn_search(const float* x, int64_t nx, const float* y, int64_t ny, int dim, int k, const int64_t* ptr_x,
                               const int64_t* ptr_y, int64_t nseg, int exclude_self, int64_t* idx, float* d2, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (dim != 2 && dim != 3) return kfail(1, "mgn_knn_search: dim must be 2 or 3");
-  if (k < 1) return kfail(1, "mgn_knn_search: k must be >= 1");
-  if (k > KNN_MAXK) return kfail(1, "mgn_knn_search: k must not exceed mgn_knn_max_k() = 32");
-  if (nseg < 1 || nseg > KNN_NMAX) return kfail(1, "mgn_knn_search: nseg must be in [1, 2^31 - 1]");
-  if (nx < 0 || nx > KNN_NMAX || ny < 0 || ny > KNN_NMAX) return kfail(1, "mgn_knn_search: nx and ny must be in [0, 2^31 - 1]");
-  if (ny * k > KNN_NMAX) return kfail(1, "mgn_knn_search: ny * k must be below 2^31");
-  if (!ptr_x || !ptr_y) return kfail(1, "mgn_knn_search: ptr_x / ptr_y must not be null");
-  if (nx > 0 && !x) return kfail(1, "mgn_knn_search: x must not be null");
-  if (ny > 0 && (!y || !idx || !d2)) return kfail(1, "mgn_knn_search: y / idx / d2 must not be null");
+  if (dim != 2 && dim != 3) return fail(1, "mgn_knn_search: dim must be 2 or 3");
+  if (k < 1) return fail(1, "mgn_knn_search: k must be >= 1");
+  if (k > KNN_MAXK) return fail(1, "mgn_knn_search: k must not exceed mgn_knn_max_k() = 32");
+  if (nseg < 1 || nseg > KNN_NMAX) return fail(1, "mgn_knn_search: nseg must be in [1, 2^31 - 1]");
+  if (nx < 0 || nx > KNN_NMAX || ny < 0 || ny > KNN_NMAX) return fail(1, "mgn_knn_search: nx and ny must be in [0, 2^31 - 1]");
+  if (ny * k > KNN_NMAX) return fail(1, "mgn_knn_search: ny * k must be below 2^31");
+  if (!ptr_x || !ptr_y) return fail(1, "mgn_knn_search: ptr_x / ptr_y must not be null");
+  if (nx > 0 && !x) return fail(1, "mgn_knn_search: x must not be null");
+  if (ny > 0 && (!y || !idx || !d2)) return fail(1, "mgn_knn_search: y / idx / d2 must not be null");
   if (ny == 0) return 0;
   const long nb = (long)((ny + KNN_THREADS - 1) / KNN_THREADS + nseg);
-  if (nb > KNN_NMAX) return kfail(1, "mgn_knn_search: too many workgroups");
+  if (nb > KNN_NMAX) return fail(1, "mgn_knn_search: too many workgroups");
   const dim3 grid((unsigned)nb);
   if (dim == 2) knn_launch<2>(k, grid, s, x, y, ptr_x, ptr_y, (int)nseg, (long)nx, (long)ny, exclude_self ? 1 : 0, idx, d2);
   else knn_launch<3>(k, grid, s, x, y, ptr_x, ptr_y, (int)nseg, (long)nx, (long)ny, exclude_self ? 1 : 0, idx, d2);
-  return knn_check_launch("mgn_knn_search");
+  return check_launch("mgn_knn_search");
 }
 
 extern "C" int mgn_knn_interp_fwd(const float* x, int64_t nx, int F, const int64_t* idx, const float* d2, int64_t ny, int k, float* a,
                                   float* out, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (F < 1) return kfail(1, "mgn_knn_interp_fwd: F must be >= 1");
-  if (k < 1 || k > KNN_MAXK) return kfail(1, "mgn_knn_interp_fwd: k must be in [1, mgn_knn_max_k()]");
-  if (nx < 0 || nx > KNN_NMAX || ny < 0 || ny > KNN_NMAX || ny * k > KNN_NMAX) return kfail(1, "mgn_knn_interp_fwd: nx, ny, ny * k must be in [0, 2^31 - 1]");
-  if (nx > 0 && !x) return kfail(1, "mgn_knn_interp_fwd: x must not be null");
-  if (ny > 0 && (!idx || !d2 || !a || !out)) return kfail(1, "mgn_knn_interp_fwd: idx / d2 / a / out must not be null");
+  if (F < 1) return fail(1, "mgn_knn_interp_fwd: F must be >= 1");
+  if (k < 1 || k > KNN_MAXK) return fail(1, "mgn_knn_interp_fwd: k must be in [1, mgn_knn_max_k()]");
+  if (nx < 0 || nx > KNN_NMAX || ny < 0 || ny > KNN_NMAX || ny * k > KNN_NMAX) return fail(1, "mgn_knn_interp_fwd: nx, ny, ny * k must be in [0, 2^31 - 1]");
+  if (nx > 0 && !x) return fail(1, "mgn_knn_interp_fwd: x must not be null");
+  if (ny > 0 && (!idx || !d2 || !a || !out)) return fail(1, "mgn_knn_interp_fwd: idx / d2 / a / out must not be null");
   if (ny == 0) return 0;
   hipLaunchKernelGGL(k_knn_weights, dim3(knn_grid((long)ny)), dim3(256), 0, s, idx, d2, (long)ny, (long)nx, k, a);
   hipLaunchKernelGGL(k_knn_interp_fwd, dim3(knn_grid((long)ny * F)), dim3(256), 0, s, x, idx, (const float*)a, (long)ny, (long)nx, k, F, out);
-  return knn_check_launch("mgn_knn_interp_fwd");
+  return check_launch("mgn_knn_interp_fwd");
 }
 
 extern "C" int mgn_knn_interp_bwd(const float* dy, const float* a, const int32_t* rowptr, const int32_t* perm, int64_t nx, int64_t ny, int k,
                                   int F, float* dx, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (F < 1) return kfail(1, "mgn_knn_interp_bwd: F must be >= 1");
-  if (k < 1 || k > KNN_MAXK) return kfail(1, "mgn_knn_interp_bwd: k must be in [1, mgn_knn_max_k()]");
-  if (nx < 0 || nx > KNN_NMAX || ny < 0 || ny > KNN_NMAX || ny * k > KNN_NMAX) return kfail(1, "mgn_knn_interp_bwd: nx, ny, ny * k must be in [0, 2^31 - 1]");
-  if (nx > 0 && (!rowptr || !dx)) return kfail(1, "mgn_knn_interp_bwd: rowptr / dx must not be null");
-  if (nx > 0 && ny > 0 && (!dy || !a || !perm)) return kfail(1, "mgn_knn_interp_bwd: dy / a / perm must not be null");
+  if (F < 1) return fail(1, "mgn_knn_interp_bwd: F must be >= 1");
+  if (k < 1 || k > KNN_MAXK) return fail(1, "mgn_knn_interp_bwd: k must be in [1, mgn_knn_max_k()]");
+  if (nx < 0 || nx > KNN_NMAX || ny < 0 || ny > KNN_NMAX || ny * k > KNN_NMAX) return fail(1, "mgn_knn_interp_bwd: nx, ny, ny * k must be in [0, 2^31 - 1]");
+  if (nx > 0 && (!rowptr || !dx)) return fail(1, "mgn_knn_interp_bwd: rowptr / dx must not be null");
+  if (nx > 0 && ny > 0 && (!dy || !a || !perm)) return fail(1, "mgn_knn_interp_bwd: dy / a / perm must not be null");
   if (nx == 0) return 0;
   hipLaunchKernelGGL(k_knn_interp_bwd, dim3(knn_grid((long)nx * F)), dim3(256), 0, s, dy, a, rowptr, perm, (long)nx, (long)ny, k, F, dx);
-  return knn_check_launch("mgn_knn_interp_bwd");
+  return check_launch("mgn_knn_interp_bwd");
 }

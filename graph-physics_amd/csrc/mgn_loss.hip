@@ -13,20 +13,8 @@
 #include <stdio.h>
 #include "mgn_hip.h"
 
-static thread_local char g_lerr[256] = "";
-extern "C" const char* mgn_loss_last_error(void) { return g_lerr; }
-static int lfail(int code, const char* msg) {
-  snprintf(g_lerr, sizeof(g_lerr), "%s", msg);
-  return code;
-}
-static int lcheck(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    snprintf(g_lerr, sizeof(g_lerr), "%s: %s", what, hipGetErrorString(e));
-    return 2;
-  }
-  return 0;
-}
+#include "mgn_host.inc"  // g_err, fail, check_launch
+extern "C" const char* mgn_loss_last_error(void) { return g_err; }
 
 #define LF MGN_LOSS_MAX_F
 #define LD MGN_LOSS_MAX_D
@@ -149,24 +137,24 @@ __global__ void __launch_bounds__(256) k_ls_node_geom(const int64_t* __restrict_
 extern "C" int mgn_loss_fd_geometry(const int64_t* rowptr, const int32_t* col, const uint8_t* self_loop, const float* pos, int DX,
                                     int64_t N, float* coef, float* inv, void* stream) {
   if (rowptr == nullptr || pos == nullptr || inv == nullptr || N < 0 || DX < 1 || DX > LD)
-    return lfail(1, "mgn_loss_fd_geometry: bad arguments (positions of 1..3 columns)");
+    return fail(1, "mgn_loss_fd_geometry: bad arguments (positions of 1..3 columns)");
   if (N == 0) return 0;
   hipLaunchKernelGGL(k_fd_geom, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, rowptr, col, self_loop, pos, DX,
                      (long)N, coef, inv);
-  return lcheck("mgn_loss_fd_geometry");
+  return check_launch("mgn_loss_fd_geometry");
 }
 extern "C" int mgn_loss_ls_geometry(const int32_t* elems, int64_t M, int K, const float* pos, int DX, int64_t N, const int64_t* nptr,
                                     const int32_t* nent, float* cv, double* vol, float* inv, void* stream) {
   if (elems == nullptr || pos == nullptr || nptr == nullptr || nent == nullptr || cv == nullptr || vol == nullptr || inv == nullptr ||
       M < 0 || N < 0)
-    return lfail(1, "mgn_loss_ls_geometry: bad arguments");
+    return fail(1, "mgn_loss_ls_geometry: bad arguments");
   if (!((K == 3 && (DX == 2 || DX == 3)) || (K == 4 && DX == 3)))
-    return lfail(1, "mgn_loss_ls_geometry: elements are triangles in 2-D / 3-D or tetrahedra in 3-D");
-  if (M * K >= ((int64_t)1 << 31)) return lfail(1, "mgn_loss_ls_geometry: element corner count needs 32-bit entries");
+    return fail(1, "mgn_loss_ls_geometry: elements are triangles in 2-D / 3-D or tetrahedra in 3-D");
+  if (M * K >= ((int64_t)1 << 31)) return fail(1, "mgn_loss_ls_geometry: element corner count needs 32-bit entries");
   hipStream_t s = (hipStream_t)stream;
   if (M > 0) hipLaunchKernelGGL(k_ls_elem_geom, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, elems, (long)M, K, pos, DX, cv, vol);
   if (N > 0) hipLaunchKernelGGL(k_ls_node_geom, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, nptr, nent, K, (const double*)vol, (long)N, inv);
-  return lcheck("mgn_loss_ls_geometry");
+  return check_launch("mgn_loss_ls_geometry");
 }
 
 // ===================================================================== per step
@@ -540,7 +528,7 @@ extern "C" size_t mgn_loss_workspace_bytes(void) { return (size_t)(MGN_LOSS_MAX_
 extern "C" int mgn_loss_fwd(const mgn_loss_args* args, void* stream) {
   const char* why;
   if (loss_validate(args, &why)) {
-    snprintf(g_lerr, sizeof(g_lerr), "mgn_loss_fwd: %s", why);
+    snprintf(g_err, sizeof(g_err), "mgn_loss_fwd: %s", why);
     return 1;
   }
   mgn_loss_args a = *args;
@@ -554,25 +542,25 @@ extern "C" int mgn_loss_fwd(const mgn_loss_args* args, void* stream) {
   if (ls) hipLaunchKernelGGL(k_loss_node_fwd<1>, dim3(nblk), dim3(256), 0, s, a);
   else hipLaunchKernelGGL(k_loss_node_fwd<0>, dim3(nblk), dim3(256), 0, s, a);
   hipLaunchKernelGGL(k_loss_final, dim3(1), dim3(256), 0, s, a, nblk);
-  return lcheck("mgn_loss_fwd");
+  return check_launch("mgn_loss_fwd");
 }
 
 extern "C" int mgn_loss_bwd(const mgn_loss_args* args, const float* g, float* d_net, float* d_u, float* dge, void* stream) {
   const char* why;
   if (loss_validate(args, &why)) {
-    snprintf(g_lerr, sizeof(g_lerr), "mgn_loss_bwd: %s", why);
+    snprintf(g_err, sizeof(g_err), "mgn_loss_bwd: %s", why);
     return 1;
   }
-  if (g == nullptr || (d_net == nullptr && d_u == nullptr)) return lfail(1, "mgn_loss_bwd: needs the incoming gradient and an output");
+  if (g == nullptr || (d_net == nullptr && d_u == nullptr)) return fail(1, "mgn_loss_bwd: needs the incoming gradient and an output");
   mgn_loss_args a = *args;
-  if (d_u != nullptr && a.u_out == nullptr) return lfail(1, "mgn_loss_bwd: no physical fields in this loss");
+  if (d_u != nullptr && a.u_out == nullptr) return fail(1, "mgn_loss_bwd: no physical fields in this loss");
   const bool ls = d_u != nullptr && a.method == MGN_LOSS_LEAST_SQUARES;
-  if (ls && dge == nullptr) return lfail(1, "mgn_loss_bwd: least_squares needs the [M, F, DX] scratch");
+  if (ls && dge == nullptr) return fail(1, "mgn_loss_bwd: least_squares needs the [M, F, DX] scratch");
   if (a.N == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
   const unsigned nb = (unsigned)((a.N + NODES_PER_BLOCK - 1) / NODES_PER_BLOCK);
   if (ls && a.M > 0) hipLaunchKernelGGL(k_ls_elem_bwd, dim3((unsigned)((a.M + 255) / 256)), dim3(256), 0, s, a, dge);
   if (ls) hipLaunchKernelGGL(k_loss_node_bwd<1>, dim3(nb), dim3(256), 0, s, a, g, d_net, d_u, (const float*)dge);
   else hipLaunchKernelGGL(k_loss_node_bwd<0>, dim3(nb), dim3(256), 0, s, a, g, d_net, d_u, (const float*)dge);
-  return lcheck("mgn_loss_bwd");
+  return check_launch("mgn_loss_bwd");
 }

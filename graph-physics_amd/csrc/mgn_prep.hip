@@ -4,33 +4,17 @@
 // inverse-normalise + ground-truth re-imposition).  All of it is HBM-bound integer / elementwise
 // work: one pass per tensor, coalesced rows, no atomics (two-stage column statistics).
 // Second translation unit of libmgn_hip.so; the sort / unique primitives are rocPRIM (header-only).
-#include <hip/hip_runtime.h>
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_select.hpp>
-#include <stdint.h>
-#include <stdio.h>
 #include "mgn_hip.h"
+#include "mgn_host.inc"       // g_err, fail, check_launch, workspace carving
+#include "mgn_graphprim.inc"  // edge keys, sort_unique_keys
 
-static thread_local char g_perr[256] = "";
-extern "C" const char* mgn_prep_last_error(void) { return g_perr; }
-static int pfail(int code, const char* msg) {
-  snprintf(g_perr, sizeof(g_perr), "%s", msg);
-  return code;
-}
-static int pcheck(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    snprintf(g_perr, sizeof(g_perr), "%s: %s", what, hipGetErrorString(e));
-    return 2;
-  }
-  return 0;
-}
+extern "C" const char* mgn_prep_last_error(void) { return g_err; }
 
 // ===================================================================== faces -> edges
 // T.FaceToEdge(remove_faces=False) + to_undirected (reference dataset/preprocessing.py:421-424;
 // torch-geometric 2.6.1): every pair of corners of a face in both directions, coalesced =
 // sorted by (src, dst), duplicates removed; self loops of degenerate faces dropped.
-// key = src * N + dst; invalid corner (outside [0,N)) -> err flag, key = all ones (sorts last).
+// Keys as in mgn_graphprim.inc; invalid corner (outside [0,N)) -> err flag, the face's pairs are dropped.
 __global__ void k_face_keys(const int64_t* __restrict__ face, int K, long F, long N, uint64_t* __restrict__ keys, int* __restrict__ err) {
   const long f = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (f >= F) return;
@@ -46,16 +30,15 @@ __global__ void k_face_keys(const int64_t* __restrict__ face, int K, long F, lon
   for (int a = 0; a < K; ++a)
     for (int b = a + 1; b < K; ++b, ++p) {
       const bool keep = ok && v[a] != v[b];
-      keys[(size_t)p * F + f] = keep ? (uint64_t)v[a] * (uint64_t)N + (uint64_t)v[b] : ~0ull;
-      keys[(size_t)(npair + p) * F + f] = keep ? (uint64_t)v[b] * (uint64_t)N + (uint64_t)v[a] : ~0ull;
+      keys[(size_t)p * F + f] = keep ? edge_key(v[a], v[b], N) : EDGE_KEY_DROPPED;
+      keys[(size_t)(npair + p) * F + f] = keep ? edge_key(v[b], v[a], N) : EDGE_KEY_DROPPED;
     }
 }
 
 __global__ void k_decode_keys(const uint64_t* __restrict__ uniq, const size_t* __restrict__ n_uniq, long N, long cap,
                               int64_t* __restrict__ src, int64_t* __restrict__ dst, int64_t* __restrict__ n_edges) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  size_t n = *n_uniq;
-  if (n > 0 && uniq[n - 1] == ~0ull) --n;  // the dropped pairs collapse into one trailing key
+  const size_t n = edge_key_count(uniq, n_uniq);
   if (i == 0) *n_edges = (int64_t)n;
   if (i >= cap || (size_t)i >= n) return;
   const uint64_t k = uniq[i];
@@ -68,19 +51,16 @@ struct F2EPlan {
 };
 static F2EPlan f2e_plan(int64_t F, int K) {
   F2EPlan p;
+  WsCarver c;
   const size_t n = (size_t)F * K * (K - 1);
-  size_t t1 = 0, t2 = 0;
-  rocprim::radix_sort_keys(nullptr, t1, (uint64_t*)nullptr, (uint64_t*)nullptr, n, 0, 64, (hipStream_t)0);
-  rocprim::unique(nullptr, t2, (uint64_t*)nullptr, (uint64_t*)nullptr, (size_t*)nullptr, n, rocprim::equal_to<uint64_t>(), (hipStream_t)0);
-  p.tmp_bytes = (t1 > t2 ? t1 : t2) + 256;
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  p.keys = 0;
-  p.sorted = al(p.keys + n * 8);
-  p.uniq = al(p.sorted + n * 8);
-  p.count = al(p.uniq + n * 8);
+  p.tmp_bytes = sort_unique_tmp_bytes(n);
+  p.keys = c.take(n * 8);
+  p.sorted = c.take(n * 8);
+  p.uniq = c.take(n * 8);
+  p.count = c.take(128);
   p.err = p.count + 64;
-  p.tmp = al(p.err + 64);
-  p.total = p.tmp + p.tmp_bytes;
+  p.tmp = c.take(p.tmp_bytes);
+  p.total = c.end;
   return p;
 }
 
@@ -92,33 +72,28 @@ extern "C" size_t mgn_faces_to_edges_workspace_bytes(int64_t F, int K) {
 extern "C" int mgn_faces_to_edges(const int64_t* face, int K, int64_t F, int64_t N, int64_t* src, int64_t* dst,
                                   int64_t* n_edges, void* ws, size_t ws_bytes, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (K != 3 && K != 4) return pfail(1, "mgn_faces_to_edges: faces must have 3 or 4 corners");
-  if (F < 0 || N < 1 || N > 3037000499LL) return pfail(1, "mgn_faces_to_edges: size out of range (N*N must fit 63 bits)");
+  if (K != 3 && K != 4) return fail(1, "mgn_faces_to_edges: faces must have 3 or 4 corners");
+  if (F < 0 || N < 1 || N > 3037000499LL) return fail(1, "mgn_faces_to_edges: size out of range (N*N must fit 63 bits)");
   const F2EPlan p = f2e_plan(F, K);
-  const size_t base = ((size_t)ws + 255) & ~(size_t)255;
-  if (ws_bytes < (base - (size_t)ws) + p.total) return pfail(1, "mgn_faces_to_edges: workspace too small");
-  char* w = (char*)base;
+  char* w = ws_base(ws, ws_bytes, p.total);
+  if (!w) return fail(1, "mgn_faces_to_edges: workspace too small");
   uint64_t *keys = (uint64_t*)(w + p.keys), *sorted = (uint64_t*)(w + p.sorted), *uniq = (uint64_t*)(w + p.uniq);
   size_t* count = (size_t*)(w + p.count);
   int* err = (int*)(w + p.err);
   const size_t n = (size_t)F * K * (K - 1);
-  if (hipMemsetAsync(count, 0, 128, s) != hipSuccess) return pfail(2, "mgn_faces_to_edges: memset");
+  if (hipMemsetAsync(count, 0, 128, s) != hipSuccess) return fail(2, "mgn_faces_to_edges: memset");
   if (n == 0) {
-    if (hipMemsetAsync(n_edges, 0, sizeof(int64_t), s) != hipSuccess) return pfail(2, "mgn_faces_to_edges: memset");
+    if (hipMemsetAsync(n_edges, 0, sizeof(int64_t), s) != hipSuccess) return fail(2, "mgn_faces_to_edges: memset");
     return 0;
   }
   hipLaunchKernelGGL(k_face_keys, dim3((unsigned)((F + 255) / 256)), dim3(256), 0, s, face, K, (long)F, (long)N, keys, err);
-  size_t tb = p.tmp_bytes;
-  if (rocprim::radix_sort_keys(w + p.tmp, tb, keys, sorted, n, 0, 64, s) != hipSuccess) return pfail(2, "mgn_faces_to_edges: sort");
-  tb = p.tmp_bytes;
-  if (rocprim::unique(w + p.tmp, tb, sorted, uniq, count, n, rocprim::equal_to<uint64_t>(), s) != hipSuccess)
-    return pfail(2, "mgn_faces_to_edges: unique");
+  if (int rc = sort_unique_keys(w + p.tmp, p.tmp_bytes, keys, sorted, uniq, count, n, s, "mgn_faces_to_edges")) return rc;
   hipLaunchKernelGGL(k_decode_keys, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, uniq, count, (long)N, (long)n, src, dst, n_edges);
-  if (int rc = pcheck("mgn_faces_to_edges")) return rc;
+  if (int rc = check_launch("mgn_faces_to_edges")) return rc;
   int herr = 0;
-  if (hipMemcpyAsync(&herr, err, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess) return pfail(2, "mgn_faces_to_edges: memcpy");
-  if (hipStreamSynchronize(s) != hipSuccess) return pfail(2, "mgn_faces_to_edges: sync failed");
-  if (herr) return pfail(3, "mgn_faces_to_edges: face corner outside [0, N)");
+  if (hipMemcpyAsync(&herr, err, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess) return fail(2, "mgn_faces_to_edges: memcpy");
+  if (hipStreamSynchronize(s) != hipSuccess) return fail(2, "mgn_faces_to_edges: sync failed");
+  if (herr) return fail(3, "mgn_faces_to_edges: face corner outside [0, N)");
   return 0;
 }
 
@@ -205,16 +180,16 @@ struct MortonPlan {
 };
 static MortonPlan morton_plan(int64_t N) {
   MortonPlan p;
+  WsCarver c;
   size_t t = 0;
   rocprim::radix_sort_pairs(nullptr, t, (uint64_t*)nullptr, (uint64_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, (size_t)N, 0, 64, (hipStream_t)0);
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
   p.tmp_bytes = t + 256;
-  p.keys = 0;
-  p.keys2 = al((size_t)N * 8);
-  p.ids = al(p.keys2 + (size_t)N * 8);
-  p.box = al(p.ids + (size_t)N * 4);
-  p.tmp = al(p.box + 64);
-  p.total = p.tmp + p.tmp_bytes;
+  p.keys = c.take((size_t)N * 8);
+  p.keys2 = c.take((size_t)N * 8);
+  p.ids = c.take((size_t)N * 4);
+  p.box = c.take(64);
+  p.tmp = c.take(p.tmp_bytes);
+  p.total = c.end;
   return p;
 }
 extern "C" size_t mgn_morton_order_workspace_bytes(int64_t N) { return N < 0 ? 0 : morton_plan(N).total + 256; }
@@ -222,25 +197,24 @@ extern "C" int mgn_morton_order(const float* pos, int ld, int D, int64_t N, int3
                                 void* stream) {
   hipStream_t s = (hipStream_t)stream;
   if (pos == nullptr || order == nullptr || rank == nullptr || (D != 2 && D != 3) || ld < D || N < 0 || N > 2147483647LL)
-    return pfail(1, "mgn_morton_order: bad arguments (positions with 2 or 3 coordinates)");
+    return fail(1, "mgn_morton_order: bad arguments (positions with 2 or 3 coordinates)");
   if (N == 0) return 0;
   const MortonPlan p = morton_plan(N);
-  const size_t base = ((size_t)ws + 255) & ~(size_t)255;
-  if (ws == nullptr || ws_bytes < (base - (size_t)ws) + p.total) return pfail(1, "mgn_morton_order: workspace too small");
-  char* w = (char*)base;
+  char* w = ws_base(ws, ws_bytes, p.total);
+  if (!w) return fail(1, "mgn_morton_order: workspace too small");
   uint64_t *keys = (uint64_t*)(w + p.keys), *keys2 = (uint64_t*)(w + p.keys2);
   int32_t* ids = (int32_t*)(w + p.ids);
   unsigned* box = (unsigned*)(w + p.box);
   if (hipMemsetAsync(box, 0xff, 12, s) != hipSuccess || hipMemsetAsync(box + 3, 0, 12, s) != hipSuccess)
-    return pfail(2, "mgn_morton_order: memset");
+    return fail(2, "mgn_morton_order: memset");
   const unsigned nb = (unsigned)((N + 255) / 256);
   hipLaunchKernelGGL(k_bbox, dim3(nb < 1024 ? nb : 1024), dim3(256), 0, s, pos, ld, D, (long)N, box);
   hipLaunchKernelGGL(k_morton_keys, dim3(nb), dim3(256), 0, s, pos, ld, D, (long)N, box, keys, ids);
   size_t tb = p.tmp_bytes;
   if (rocprim::radix_sort_pairs(w + p.tmp, tb, keys, keys2, ids, order, (size_t)N, 0, 64, s) != hipSuccess)
-    return pfail(2, "mgn_morton_order: sort");
+    return fail(2, "mgn_morton_order: sort");
   hipLaunchKernelGGL(k_inverse_perm, dim3(nb), dim3(256), 0, s, order, (long)N, rank);
-  return pcheck("mgn_morton_order");
+  return check_launch("mgn_morton_order");
 }
 
 // ======================================================================= world edges
@@ -284,27 +258,14 @@ __global__ void __launch_bounds__(WE_TILE) k_world_pairs(const float* __restrict
         if (s <= r2) {
           const unsigned long long at = atomicAdd(count, 2ull);
           if (at + 1 < cap) {
-            const uint64_t jj = (uint64_t)(j0 + k);
-            keys[at] = (uint64_t)i * (uint64_t)N + jj;
-            keys[at + 1] = jj * (uint64_t)N + (uint64_t)i;
+            const int64_t jj = j0 + k;
+            keys[at] = edge_key(i, jj, N);
+            keys[at + 1] = edge_key(jj, i, N);
           }
         }
       }
     }
   }
-}
-
-__global__ void k_edge_keys(const int64_t* __restrict__ src, const int64_t* __restrict__ dst, long E, long N, uint64_t* __restrict__ keys, int* __restrict__ err) {
-  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= E) return;
-  const int64_t a = src[e], b = dst[e];
-  if (a < 0 || a >= N || b < 0 || b >= N) {
-    *err = 1;
-    keys[e] = keys[E + e] = ~0ull;
-    return;
-  }
-  keys[e] = (uint64_t)a * (uint64_t)N + (uint64_t)b;      // to_undirected: both directions
-  keys[E + e] = (uint64_t)b * (uint64_t)N + (uint64_t)a;
 }
 
 // ws layout: [keys cap][sorted cap][uniq cap][count, err][rocPRIM temp]
@@ -313,17 +274,14 @@ struct WEPlan {
 };
 static WEPlan we_plan(size_t cap) {
   WEPlan p;
-  size_t t1 = 0, t2 = 0;
-  rocprim::radix_sort_keys(nullptr, t1, (uint64_t*)nullptr, (uint64_t*)nullptr, cap, 0, 64, (hipStream_t)0);
-  rocprim::unique(nullptr, t2, (uint64_t*)nullptr, (uint64_t*)nullptr, (size_t*)nullptr, cap, rocprim::equal_to<uint64_t>(), (hipStream_t)0);
-  p.tmp_bytes = (t1 > t2 ? t1 : t2) + 256;
-  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  p.keys = 0;
-  p.sorted = al(cap * 8);
-  p.uniq = al(p.sorted + cap * 8);
-  p.count = al(p.uniq + cap * 8);
-  p.tmp = al(p.count + 256);
-  p.total = p.tmp + p.tmp_bytes;
+  WsCarver c;
+  p.tmp_bytes = sort_unique_tmp_bytes(cap);
+  p.keys = c.take(cap * 8);
+  p.sorted = c.take(cap * 8);
+  p.uniq = c.take(cap * 8);
+  p.count = c.take(256);
+  p.tmp = c.take(p.tmp_bytes);
+  p.total = c.end;
   return p;
 }
 
@@ -336,38 +294,33 @@ extern "C" int mgn_add_world_edges(const float* x, int x_w, int pos_start, int D
                                    const int64_t* src_in, const int64_t* dst_in, int64_t E, int64_t max_world_pairs,
                                    int64_t* src, int64_t* dst, int64_t* n_edges, void* ws, size_t ws_bytes, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (D != 2 && D != 3) return pfail(1, "mgn_add_world_edges: world positions must be 2-D or 3-D");
-  if (N < 1 || N > 3037000499LL || E < 0 || max_world_pairs < 0) return pfail(1, "mgn_add_world_edges: size out of range");
+  if (D != 2 && D != 3) return fail(1, "mgn_add_world_edges: world positions must be 2-D or 3-D");
+  if (N < 1 || N > 3037000499LL || E < 0 || max_world_pairs < 0) return fail(1, "mgn_add_world_edges: size out of range");
   const size_t cap = 2 * (size_t)E + 2 * (size_t)max_world_pairs + 1;
   const WEPlan p = we_plan(cap);
-  const size_t base = ((size_t)ws + 255) & ~(size_t)255;
-  if (ws_bytes < (base - (size_t)ws) + p.total) return pfail(1, "mgn_add_world_edges: workspace too small");
-  char* w = (char*)base;
+  char* w = ws_base(ws, ws_bytes, p.total);
+  if (!w) return fail(1, "mgn_add_world_edges: workspace too small");
   uint64_t *keys = (uint64_t*)(w + p.keys), *sorted = (uint64_t*)(w + p.sorted), *uniq = (uint64_t*)(w + p.uniq);
   unsigned long long* count = (unsigned long long*)(w + p.count);  // [0] world keys appended, [1] unique count (size_t), [2] err
   size_t* n_uniq = (size_t*)(count + 1);
   int* err = (int*)(count + 2);
-  if (hipMemsetAsync(count, 0, 64, s) != hipSuccess) return pfail(2, "mgn_add_world_edges: memset");
-  if (hipMemsetAsync(keys, 0xff, cap * 8, s) != hipSuccess) return pfail(2, "mgn_add_world_edges: memset");  // unused slots sort last
-  if (E > 0) hipLaunchKernelGGL(k_edge_keys, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, s, src_in, dst_in, (long)E, (long)N, keys, err);
+  if (hipMemsetAsync(count, 0, 64, s) != hipSuccess) return fail(2, "mgn_add_world_edges: memset");
+  if (hipMemsetAsync(keys, 0xff, cap * 8, s) != hipSuccess) return fail(2, "mgn_add_world_edges: memset");  // unused slots sort last
+  if (E > 0) hipLaunchKernelGGL(k_edge_list_keys<true>, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, s, src_in, dst_in, (long)E, (long)N, keys, err);
   const unsigned grid = (unsigned)((N + WE_TILE - 1) / WE_TILE);
   const unsigned long long wcap = 2ull * (unsigned long long)max_world_pairs;
   if (D == 2)
     hipLaunchKernelGGL(k_world_pairs<2>, dim3(grid), dim3(WE_TILE), 0, s, x, x_w, pos_start, type_idx, (long)N, radius * radius, keys + 2 * E, count, wcap);
   else
     hipLaunchKernelGGL(k_world_pairs<3>, dim3(grid), dim3(WE_TILE), 0, s, x, x_w, pos_start, type_idx, (long)N, radius * radius, keys + 2 * E, count, wcap);
-  size_t tb = p.tmp_bytes;
-  if (rocprim::radix_sort_keys(w + p.tmp, tb, keys, sorted, cap, 0, 64, s) != hipSuccess) return pfail(2, "mgn_add_world_edges: sort");
-  tb = p.tmp_bytes;
-  if (rocprim::unique(w + p.tmp, tb, sorted, uniq, n_uniq, cap, rocprim::equal_to<uint64_t>(), s) != hipSuccess)
-    return pfail(2, "mgn_add_world_edges: unique");
+  if (int rc = sort_unique_keys(w + p.tmp, p.tmp_bytes, keys, sorted, uniq, n_uniq, cap, s, "mgn_add_world_edges")) return rc;
   hipLaunchKernelGGL(k_decode_keys, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, s, uniq, n_uniq, (long)N, (long)cap, src, dst, n_edges);
-  if (int rc = pcheck("mgn_add_world_edges")) return rc;
+  if (int rc = check_launch("mgn_add_world_edges")) return rc;
   unsigned long long h[3] = {0, 0, 0};
-  if (hipMemcpyAsync(h, count, sizeof(h), hipMemcpyDeviceToHost, s) != hipSuccess) return pfail(2, "mgn_add_world_edges: memcpy");
-  if (hipStreamSynchronize(s) != hipSuccess) return pfail(2, "mgn_add_world_edges: sync failed");
-  if (*(int*)&h[2]) return pfail(3, "mgn_add_world_edges: edge index outside [0, N)");
-  if (h[0] > wcap) return pfail(4, "mgn_add_world_edges: more world pairs than max_world_pairs");
+  if (hipMemcpyAsync(h, count, sizeof(h), hipMemcpyDeviceToHost, s) != hipSuccess) return fail(2, "mgn_add_world_edges: memcpy");
+  if (hipStreamSynchronize(s) != hipSuccess) return fail(2, "mgn_add_world_edges: sync failed");
+  if (*(int*)&h[2]) return fail(3, "mgn_add_world_edges: edge index outside [0, N)");
+  if (h[0] > wcap) return fail(4, "mgn_add_world_edges: more world pairs than max_world_pairs");
   return 0;
 }
 
@@ -395,14 +348,14 @@ __global__ void k_edge_features(const float* __restrict__ pos, const int64_t* __
 
 extern "C" int mgn_edge_features(const float* pos, int D, const int64_t* src, const int64_t* dst, int64_t E, float* edge_attr, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (D != 2 && D != 3) return pfail(1, "mgn_edge_features: positions must be 2-D or 3-D");
+  if (D != 2 && D != 3) return fail(1, "mgn_edge_features: positions must be 2-D or 3-D");
   if (E <= 0) return 0;
   const unsigned grid = (unsigned)((E + 255) / 256);
   if (D == 2)
     hipLaunchKernelGGL(k_edge_features<2>, dim3(grid), dim3(256), 0, s, pos, src, dst, (long)E, edge_attr);
   else
     hipLaunchKernelGGL(k_edge_features<3>, dim3(grid), dim3(256), 0, s, pos, src, dst, (long)E, edge_attr);
-  return pcheck("mgn_edge_features");
+  return check_launch("mgn_edge_features");
 }
 
 // ========================================================= Simulator pre / post (N1)
@@ -510,18 +463,18 @@ extern "C" int mgn_sim_pre(const mgn_sim_desc* desc, void* ws, size_t ws_bytes, 
   hipStream_t s = (hipStream_t)stream;
   const int Wn = (d.feat_end - d.feat_start) + MGN_NODE_TYPES;
   if (d.feat_end < d.feat_start || Wn > SIM_MAXW || d.out_w < 1 || d.out_w > SIM_MAXW || d.edge_w > SIM_MAXW)
-    return pfail(1, "mgn_sim_pre: feature widths out of range (<= 32 columns per stream)");
-  if (d.N < 0 || d.E < 0 || d.x == nullptr) return pfail(1, "mgn_sim_pre: bad arguments");
+    return fail(1, "mgn_sim_pre: feature widths out of range (<= 32 columns per stream)");
+  if (d.N < 0 || d.E < 0 || d.x == nullptr) return fail(1, "mgn_sim_pre: bad arguments");
   if (d.feat_start < 0 || d.feat_end > d.x_w || d.type_idx < 0 || d.type_idx >= d.x_w)
-    return pfail(1, "mgn_sim_pre: feature / node-type columns outside x");
+    return fail(1, "mgn_sim_pre: feature / node-type columns outside x");
   if (d.y != nullptr && (d.out_start < 0 || d.out_start + d.out_w > d.x_w || d.out_w > d.y_w))
-    return pfail(1, "mgn_sim_pre: output columns outside x / y");
-  if (Wn != d.norm_w[0]) return pfail(1, "mgn_sim_pre: node feature width differs from the node normaliser's");
-  if (d.y != nullptr && d.out_w != d.norm_w[1]) return pfail(1, "mgn_sim_pre: output width differs from the output normaliser's");
-  if (d.edge_attr != nullptr && d.edge_w != d.norm_w[2]) return pfail(1, "mgn_sim_pre: edge feature width differs from the edge normaliser's");
-  if (d.target_out != nullptr && d.y == nullptr) return pfail(1, "mgn_sim_pre: target requested without y");
+    return fail(1, "mgn_sim_pre: output columns outside x / y");
+  if (Wn != d.norm_w[0]) return fail(1, "mgn_sim_pre: node feature width differs from the node normaliser's");
+  if (d.y != nullptr && d.out_w != d.norm_w[1]) return fail(1, "mgn_sim_pre: output width differs from the output normaliser's");
+  if (d.edge_attr != nullptr && d.edge_w != d.norm_w[2]) return fail(1, "mgn_sim_pre: edge feature width differs from the edge normaliser's");
+  if (d.target_out != nullptr && d.y == nullptr) return fail(1, "mgn_sim_pre: target requested without y");
   if (d.accumulate[0] || d.accumulate[1] || d.accumulate[2]) {
-    if (ws_bytes < mgn_sim_workspace_bytes()) return pfail(1, "mgn_sim_pre: workspace too small");
+    if (ws_bytes < mgn_sim_workspace_bytes()) return fail(1, "mgn_sim_pre: workspace too small");
     hipLaunchKernelGGL(k_stats_partial, dim3(SIM_PART, 3), dim3(256), 0, s, d, (float*)ws);
     hipLaunchKernelGGL(k_stats_final, dim3(3), dim3(64), 0, s, d, (const float*)ws);
   }
@@ -529,7 +482,7 @@ extern "C" int mgn_sim_pre(const mgn_sim_desc* desc, void* ws, size_t ws_bytes, 
   if (d.N * d.out_w > mx) mx = d.N * d.out_w;
   if (d.E * d.edge_w > mx) mx = d.E * d.edge_w;
   if (mx > 0) hipLaunchKernelGGL(k_sim_normalize, dim3((unsigned)((mx + 255) / 256), 3), dim3(256), 0, s, d);
-  return pcheck("mgn_sim_pre");
+  return check_launch("mgn_sim_pre");
 }
 
 // build_outputs + the rollout's ground-truth re-imposition (simulator.py:186-191,
@@ -559,12 +512,12 @@ __global__ void __launch_bounds__(256) k_sim_post(const float* __restrict__ x, i
 extern "C" int mgn_sim_post(const float* x, int x_w, int out_start, int type_idx, const float* y, int y_w, const float* net_out,
                             int O, const float* acc_sum, const float* acc_sumsq, const float* acc_count, float std_eps,
                             int mask_truth, int64_t N, float* pred, void* stream) {
-  if (O < 1 || O > SIM_MAXW || N < 0) return pfail(1, "mgn_sim_post: bad arguments");
-  if (mask_truth && y == nullptr) return pfail(1, "mgn_sim_post: ground-truth re-imposition needs y");
+  if (O < 1 || O > SIM_MAXW || N < 0) return fail(1, "mgn_sim_post: bad arguments");
+  if (mask_truth && y == nullptr) return fail(1, "mgn_sim_post: ground-truth re-imposition needs y");
   if (N == 0) return 0;
   hipLaunchKernelGGL(k_sim_post, dim3((unsigned)((N * O + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, x_w, out_start, type_idx, y,
                      y_w, net_out, O, acc_sum, acc_sumsq, acc_count, std_eps, mask_truth, (long)N, pred);
-  return pcheck("mgn_sim_post");
+  return check_launch("mgn_sim_post");
 }
 
 // =============================================== fused gradient clipping + AdamW (R8)
@@ -667,12 +620,12 @@ extern "C" size_t mgn_clip_adamw_workspace_bytes(int n, const mgn_opt_tensor* t)
 extern "C" int mgn_clip_adamw(int n, const mgn_opt_tensor* t, float max_norm, const float* lr, float* step, float beta1, float beta2,
                               float eps, float weight_decay, float* grad_norm_out, void* ws, size_t ws_bytes, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (n < 1 || lr == nullptr || step == nullptr) return pfail(1, "mgn_clip_adamw: bad arguments");
-  if (ws_bytes < mgn_clip_adamw_workspace_bytes(n, t)) return pfail(1, "mgn_clip_adamw: workspace too small");
+  if (n < 1 || lr == nullptr || step == nullptr) return fail(1, "mgn_clip_adamw: bad arguments");
+  if (ws_bytes < mgn_clip_adamw_workspace_bytes(n, t)) return fail(1, "mgn_clip_adamw: workspace too small");
   int total_parts = 0;
   for (int i = 0; i < n; ++i) {
     if (t[i].p == nullptr || t[i].g == nullptr || t[i].m == nullptr || t[i].v == nullptr || t[i].n < 0 || t[i].n > 2147483647LL)
-      return pfail(1, "mgn_clip_adamw: null tensor / size out of range");
+      return fail(1, "mgn_clip_adamw: null tensor / size out of range");
     total_parts += opt_blocks(t[i].n);
   }
   float* part = (float*)ws;
@@ -699,7 +652,7 @@ extern "C" int mgn_clip_adamw(int n, const mgn_opt_tensor* t, float max_norm, co
       part0 += b;
     }
   }
-  return pcheck("mgn_clip_adamw");
+  return check_launch("mgn_clip_adamw");
 }
 
 // ============================================================== masked mean-squared error (R8)
@@ -771,25 +724,25 @@ extern "C" int mgn_masked_mse_fwd(const float* out, int ldo, const float* tgt, i
                                   const float* types, int ntypes, float* part, float* loss, float* inv, void* stream) {
   if (out == nullptr || tgt == nullptr || type == nullptr || part == nullptr || loss == nullptr || inv == nullptr || N < 0 || O < 1 ||
       ntypes < 1 || ntypes > 4 || types == nullptr)
-    return pfail(1, "mgn_masked_mse_fwd: bad arguments (1..4 node types)");
+    return fail(1, "mgn_masked_mse_fwd: bad arguments (1..4 node types)");
   float t[4];
   for (int k = 0; k < 4; ++k) t[k] = types[k < ntypes ? k : 0];
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(k_mse_partial, dim3(MSE_PART), dim3(256), 0, s, out, ldo, tgt, ldt, type, ldty, (long)N, O, t[0], t[1], t[2], t[3], part);
   hipLaunchKernelGGL(k_mse_final, dim3(1), dim3(256), 0, s, (const float*)part, O, loss, inv);
-  return pcheck("mgn_masked_mse_fwd");
+  return check_launch("mgn_masked_mse_fwd");
 }
 extern "C" int mgn_masked_mse_bwd(const float* out, int ldo, const float* tgt, int ldt, const float* type, int ldty, int64_t N, int O,
                                   const float* types, int ntypes, const float* inv, const float* g, float* d_out, void* stream) {
   if (out == nullptr || tgt == nullptr || type == nullptr || inv == nullptr || g == nullptr || d_out == nullptr || N < 0 || O < 1 ||
       ntypes < 1 || ntypes > 4 || types == nullptr)
-    return pfail(1, "mgn_masked_mse_bwd: bad arguments (1..4 node types)");
+    return fail(1, "mgn_masked_mse_bwd: bad arguments (1..4 node types)");
   if (N == 0) return 0;
   float t[4];
   for (int k = 0; k < 4; ++k) t[k] = types[k < ntypes ? k : 0];
   hipLaunchKernelGGL(k_mse_bwd, dim3((unsigned)((N * O + 255) / 256)), dim3(256), 0, (hipStream_t)stream, out, ldo, tgt, ldt, type, ldty,
                      (long)N, O, t[0], t[1], t[2], t[3], inv, g, d_out);
-  return pcheck("mgn_masked_mse_bwd");
+  return check_launch("mgn_masked_mse_bwd");
 }
 
 // ---- the same tail in TWO launches whatever the number of tensors (376 for the 15-round model: four launches of each kernel above,
@@ -877,17 +830,17 @@ extern "C" size_t mgn_clip_adamw_table_bytes(int n, const mgn_opt_tensor* t) {
 // builds the device table of the tensors' FIXED fields (p, m, v, n; the g fields are ignored) -- a blocking host-to-device copy,
 // once per parameter set, outside any stream capture
 extern "C" int mgn_clip_adamw_table(int n, const mgn_opt_tensor* t, void* table, size_t table_bytes) {
-  if (n < 1 || n > OPT_MAX_G || table == nullptr) return pfail(1, "mgn_clip_adamw_table: bad arguments (at most 480 tensors)");
-  if (table_bytes < opt_table_bytes(n, t)) return pfail(1, "mgn_clip_adamw_table: table too small");
+  if (n < 1 || n > OPT_MAX_G || table == nullptr) return fail(1, "mgn_clip_adamw_table: bad arguments (at most 480 tensors)");
+  if (table_bytes < opt_table_bytes(n, t)) return fail(1, "mgn_clip_adamw_table: table too small");
   size_t blocks = 0;
   for (int i = 0; i < n; ++i) {
     if (t[i].p == nullptr || t[i].m == nullptr || t[i].v == nullptr || t[i].n < 0 || t[i].n > 2147483647LL)
-      return pfail(1, "mgn_clip_adamw_table: null tensor / size out of range");
+      return fail(1, "mgn_clip_adamw_table: null tensor / size out of range");
     blocks += (size_t)opt_blocks(t[i].n);
   }
   const size_t bytes = (size_t)n * sizeof(OptStatic) + blocks * sizeof(int);
   char* host = (char*)malloc(bytes);
-  if (host == nullptr) return pfail(2, "mgn_clip_adamw_table: out of host memory");
+  if (host == nullptr) return fail(2, "mgn_clip_adamw_table: out of host memory");
   OptStatic* tab = (OptStatic*)host;
   int* b2t = (int*)(host + (size_t)n * sizeof(OptStatic));
   int b = 0;
@@ -899,20 +852,20 @@ extern "C" int mgn_clip_adamw_table(int n, const mgn_opt_tensor* t, void* table,
   }
   const hipError_t e = hipMemcpy(table, host, bytes, hipMemcpyHostToDevice);
   free(host);
-  if (e != hipSuccess) return pfail(2, "mgn_clip_adamw_table: copy failed");
+  if (e != hipSuccess) return fail(2, "mgn_clip_adamw_table: copy failed");
   return 0;
 }
 // the step itself: g[i] = this step's gradient of tensor i of the table; two launches; ws as for mgn_clip_adamw
 extern "C" int mgn_clip_adamw_t(int n, const mgn_opt_tensor* t, const void* table, float max_norm, const float* lr, float* step, float beta1,
                                 float beta2, float eps, float weight_decay, float* grad_norm_out, void* ws, size_t ws_bytes, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (n < 1 || n > OPT_MAX_G || table == nullptr || lr == nullptr || step == nullptr) return pfail(1, "mgn_clip_adamw_t: bad arguments");
-  if (ws_bytes < mgn_clip_adamw_workspace_bytes(n, t)) return pfail(1, "mgn_clip_adamw_t: workspace too small");
+  if (n < 1 || n > OPT_MAX_G || table == nullptr || lr == nullptr || step == nullptr) return fail(1, "mgn_clip_adamw_t: bad arguments");
+  if (ws_bytes < mgn_clip_adamw_workspace_bytes(n, t)) return fail(1, "mgn_clip_adamw_t: workspace too small");
   OptG L;
   L.n = n;
   int b = 0;
   for (int i = 0; i < n; ++i) {
-    if (t[i].g == nullptr) return pfail(1, "mgn_clip_adamw_t: null gradient");
+    if (t[i].g == nullptr) return fail(1, "mgn_clip_adamw_t: null gradient");
     L.g[i] = t[i].g;
     b += opt_blocks(t[i].n);
   }
@@ -923,7 +876,7 @@ extern "C" int mgn_clip_adamw_t(int n, const mgn_opt_tensor* t, const void* tabl
   hipLaunchKernelGGL(k_sumsq_partial_t, dim3(b), dim3(256), 0, s, L, part, step);
   hipLaunchKernelGGL(k_clip_adamw_t, dim3(b), dim3(256), 0, s, L, (const float*)part, lr, (const float*)step, beta1, beta2, eps, weight_decay,
                      max_norm, grad_norm_out);
-  return pcheck("mgn_clip_adamw_t");
+  return check_launch("mgn_clip_adamw_t");
 }
 
 // ============================================================== halo exchange (8e)
@@ -944,11 +897,11 @@ __global__ void __launch_bounds__(256) k_gather_rows(const float* __restrict__ s
 }
 
 extern "C" int mgn_gather_rows(const float* src, const int32_t* idx, int64_t n, int H, float* out, void* stream) {
-  if (n < 0 || H < 4 || (H & 3)) return pfail(1, "mgn_gather_rows: bad arguments");
+  if (n < 0 || H < 4 || (H & 3)) return fail(1, "mgn_gather_rows: bad arguments");
   if (n == 0) return 0;
   const long lanes = (long)n * (H / 4);
   hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, (hipStream_t)stream, src, idx, (long)n, H, out);
-  return pcheck("mgn_gather_rows");
+  return check_launch("mgn_gather_rows");
 }
 
 // dst[nodes[j], :] += sum_{k = rowptr[j]}^{rowptr[j+1]-1} rows[perm[k], :]     (k ascending: fixed order)
@@ -971,12 +924,12 @@ __global__ void __launch_bounds__(256) k_halo_unpack_add(const float* __restrict
 
 extern "C" int mgn_halo_unpack_add(const float* rows, const int32_t* nodes, const int32_t* rowptr, const int32_t* perm, int64_t n_nodes,
                                    int H, float* dst, void* stream) {
-  if (n_nodes < 0 || H < 4 || (H & 3)) return pfail(1, "mgn_halo_unpack_add: bad arguments");
+  if (n_nodes < 0 || H < 4 || (H & 3)) return fail(1, "mgn_halo_unpack_add: bad arguments");
   if (n_nodes == 0) return 0;
   const long lanes = (long)n_nodes * (H / 4);
   hipLaunchKernelGGL(k_halo_unpack_add, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, (hipStream_t)stream, rows, nodes, rowptr, perm,
                      (long)n_nodes, H, dst);
-  return pcheck("mgn_halo_unpack_add");
+  return check_launch("mgn_halo_unpack_add");
 }
 
 // ====================================================== GraphNetBlock variants (N3)
@@ -1011,19 +964,19 @@ __global__ void __launch_bounds__(256) k_gate_bwd(const float* dAggG, const floa
 
 extern "C" int mgn_gate_fwd(const float* G, const float* phi, const float* gate_pos, const float* agg, int64_t N, int H, float* gate_out,
                             float* agg_out, void* stream) {
-  if (N < 0 || H < 1 || G == nullptr || agg == nullptr || agg_out == nullptr) return pfail(1, "mgn_gate_fwd: bad arguments");
+  if (N < 0 || H < 1 || G == nullptr || agg == nullptr || agg_out == nullptr) return fail(1, "mgn_gate_fwd: bad arguments");
   if (N == 0) return 0;
   hipLaunchKernelGGL(k_gate_fwd, dim3((unsigned)((N * H + 255) / 256)), dim3(256), 0, (hipStream_t)stream, G, phi, gate_pos, agg, (long)N, H,
                      gate_out, agg_out);
-  return pcheck("mgn_gate_fwd");
+  return check_launch("mgn_gate_fwd");
 }
 
 extern "C" int mgn_gate_bwd(const float* dAggG, const float* agg, const float* gate, int64_t N, int H, float* dAgg, float* dG, void* stream) {
   if (N < 0 || H < 1 || dAggG == nullptr || agg == nullptr || gate == nullptr || dAgg == nullptr || dG == nullptr)
-    return pfail(1, "mgn_gate_bwd: bad arguments");
+    return fail(1, "mgn_gate_bwd: bad arguments");
   if (N == 0) return 0;
   hipLaunchKernelGGL(k_gate_bwd, dim3((unsigned)((N * H + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dAggG, agg, gate, (long)N, H, dAgg, dG);
-  return pcheck("mgn_gate_bwd");
+  return check_launch("mgn_gate_bwd");
 }
 
 // ---- relative RoPE on the source features (layers.py:1020-1026,1104-1149).  The first
@@ -1098,22 +1051,22 @@ __global__ void __launch_bounds__(256) k_rope_scatter(const float* __restrict__ 
 extern "C" int mgn_rope_gather(const float* x, const float* pos, int pos_w, const float* inv_freq, int pair_count, int axes,
                                const int32_t* src, const int32_t* dst, int64_t E, int H, float* out, void* stream) {
   if (E < 0 || H < 2 || (H & 1) || pair_count < 0 || axes < 1 || axes > 3 || pos_w < axes || 2 * pair_count * axes > H)
-    return pfail(1, "mgn_rope_gather: bad arguments");
+    return fail(1, "mgn_rope_gather: bad arguments");
   if (E == 0) return 0;
   hipLaunchKernelGGL(k_rope_gather, dim3((unsigned)((E * (H / 2) + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, pos, pos_w, inv_freq,
                      pair_count, axes, src, dst, (long)E, H, out);
-  return pcheck("mgn_rope_gather");
+  return check_launch("mgn_rope_gather");
 }
 
 extern "C" int mgn_rope_scatter(const float* T, const float* pos, int pos_w, const float* inv_freq, int pair_count, int axes,
                                 const int32_t* src, const int32_t* dst, const int32_t* rowptr_src, const int32_t* perm_src, int64_t N, int H,
                                 const float* resid, float* out, void* stream) {
   if (N < 0 || H < 2 || (H & 1) || pair_count < 0 || axes < 1 || axes > 3 || pos_w < axes || 2 * pair_count * axes > H)
-    return pfail(1, "mgn_rope_scatter: bad arguments");
+    return fail(1, "mgn_rope_scatter: bad arguments");
   if (N == 0) return 0;
   hipLaunchKernelGGL(k_rope_scatter, dim3((unsigned)((N * (H / 2) + 255) / 256)), dim3(256), 0, (hipStream_t)stream, T, pos, pos_w, inv_freq,
                      pair_count, axes, src, dst, rowptr_src, perm_src, (long)N, H, resid, out);
-  return pcheck("mgn_rope_scatter");
+  return check_launch("mgn_rope_scatter");
 }
 
 // ================================================================ noise injection (N2)
@@ -1157,12 +1110,12 @@ __global__ void __launch_bounds__(256) k_add_noise(float* __restrict__ x, int x_
 extern "C" int mgn_add_noise(float* x, int x_w, int64_t N, int n_ranges, const int* starts, const int* ends, const float* scales, int type_idx,
                              uint64_t seed, uint32_t offset, void* stream) {
   if (x == nullptr || N < 0 || n_ranges < 1 || n_ranges > NOISE_MAX_RANGES || type_idx < 0 || type_idx >= x_w)
-    return pfail(1, "mgn_add_noise: bad arguments (1..8 ranges)");
+    return fail(1, "mgn_add_noise: bad arguments (1..8 ranges)");
   NoiseRanges R;
   R.n = n_ranges;
   R.col0[0] = 0;
   for (int r = 0; r < n_ranges; ++r) {
-    if (starts[r] < 0 || ends[r] < starts[r] || ends[r] > x_w || ends[r] > 65535) return pfail(1, "mgn_add_noise: column range outside x");
+    if (starts[r] < 0 || ends[r] < starts[r] || ends[r] > x_w || ends[r] > 65535) return fail(1, "mgn_add_noise: column range outside x");
     R.start[r] = starts[r], R.end[r] = ends[r], R.scale[r] = scales[r];
     R.col0[r + 1] = R.col0[r] + (ends[r] - starts[r]);
   }
@@ -1170,14 +1123,14 @@ extern "C" int mgn_add_noise(float* x, int x_w, int64_t N, int n_ranges, const i
   // (the reference takes its mask BEFORE the loop, :219-222 -- a noised type column has no meaning there either)
   bool overlap = false;
   for (int r = 0; r < n_ranges; ++r) {
-    if (type_idx >= starts[r] && type_idx < ends[r]) return pfail(1, "mgn_add_noise: node_type_index lies inside a noised column range");
+    if (type_idx >= starts[r] && type_idx < ends[r]) return fail(1, "mgn_add_noise: node_type_index lies inside a noised column range");
     for (int q = 0; q < r; ++q) overlap = overlap || (starts[r] < ends[q] && starts[q] < ends[r]);
   }
   if (R.col0[n_ranges] == 0 || N == 0) return 0;
   if (!overlap) {
     const long tot = (long)N * R.col0[n_ranges];
     hipLaunchKernelGGL(k_add_noise, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, x_w, (long)N, R, type_idx, seed, offset);
-    return pcheck("mgn_add_noise");
+    return check_launch("mgn_add_noise");
   }
   // overlapping ranges: the reference applies them one after the other (:224-236); one launch per range keeps every
   // `+=` of a launch on a distinct element (no race), the stream orders the launches.  The random stream of range r is
@@ -1192,5 +1145,5 @@ extern "C" int mgn_add_noise(float* x, int x_w, int64_t N, int n_ranges, const i
     if (tot == 0) continue;
     hipLaunchKernelGGL(k_add_noise, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, x_w, (long)N, R1, type_idx, seed, offset);
   }
-  return pcheck("mgn_add_noise");
+  return check_launch("mgn_add_noise");
 }

@@ -21,22 +21,15 @@
 //           cnt[r + 1] = min(K, cnt[r] + total); after the last round a shortfall sets the error flag.  Done here, not by
 //           rocPRIM: the base offset, the truncation at K and the shortfall flag ride along, and a round that has nothing to do
 //           costs one load.
-//     fill  the same workgroups: wave64 ballot ranks + a cross-wave scan of four counts in LDS (as k_sg_fill); slot =
-//           offs[block] + rank; slots < K are written to both new column blocks.  Ordered stream compaction: acceptance order
-//           is (round, candidate index) order, never sorted-code order, and bit-identical from run to run.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <string.h>
+//     fill  the same workgroups: slot = offs[block] + rank (the ordered stream compaction of mgn_graphprim.inc); slots < K are
+//           written to both new column blocks.  Acceptance order is (round, candidate index) order, never sorted-code order,
+//           and bit-identical from run to run.
 #include "mgn_hip.h"
+#include "mgn_host.inc"       // g_err, fail, check_launch, workspace carving
+#include "mgn_graphprim.inc"  // wave_kept, block_kept, block_compact_slot
 #include "mgn_philox.inc"
 
-static thread_local char g_rerr[256] = "";
-extern "C" const char* mgn_randedge_last_error(void) { return g_rerr; }
-static int rfail(int code, const char* msg) {
-  snprintf(g_rerr, sizeof(g_rerr), "%s", msg);
-  return code;
-}
+extern "C" const char* mgn_randedge_last_error(void) { return g_err; }
 
 #define RE_THREADS 256
 #define RE_ITEMS 8
@@ -124,9 +117,7 @@ __global__ void __launch_bounds__(256) k_re_cand(int r, long M, long N, long K, 
 __global__ void __launch_bounds__(RE_THREADS) k_re_flag(int r, long M, long K, const int64_t* __restrict__ cnt,
                                                         int32_t* __restrict__ lo, const uint32_t* __restrict__ slot,
                                                         const uint32_t* __restrict__ vals, uint32_t* __restrict__ blkcnt) {
-  __shared__ unsigned s_cnt[RE_THREADS / 64];
   if (cnt[r] >= K) return;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long base = (long)blockIdx.x * RE_BLOCK;
   unsigned kept = 0;  // wave-uniform
   for (int p = 0; p < RE_ITEMS; ++p) {
@@ -136,15 +127,10 @@ __global__ void __launch_bounds__(RE_THREADS) k_re_flag(int r, long M, long K, c
       keep = vals[slot[c]] == (uint32_t)((long)r * M + c + 1);
       if (!keep) lo[c] = -1;
     }
-    kept += (unsigned)__popcll(__ballot(keep));
+    kept += wave_kept(keep);
   }
-  if (lane == 0) s_cnt[wave] = kept;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned t = 0;
-    for (int w = 0; w < RE_THREADS / 64; ++w) t += s_cnt[w];
-    blkcnt[blockIdx.x] = t;
-  }
+  const unsigned t = block_kept<RE_THREADS>(kept);
+  if (threadIdx.x == 0) blkcnt[blockIdx.x] = t;
 }
 
 // one workgroup: offs[b] = cnt[r] + sum of blkcnt[0 .. b)
@@ -178,34 +164,19 @@ __global__ void __launch_bounds__(RE_THREADS) k_re_fill(int r, long M, long K, l
                                                         const int32_t* __restrict__ lo, const int32_t* __restrict__ hi,
                                                         const int64_t* __restrict__ offs, int64_t* __restrict__ out0,
                                                         int64_t* __restrict__ out1) {
-  __shared__ unsigned s_cnt[2][RE_THREADS / 64];  // double-buffered: one barrier per pass
   if (cnt[r] >= K) return;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long base = (long)blockIdx.x * RE_BLOCK;
   int64_t at = offs[blockIdx.x];  // slot of this workgroup's first kept candidate
   for (int p = 0; p < RE_ITEMS; ++p) {
     const long c = base + (long)p * RE_THREADS + threadIdx.x;
     const int32_t l = c < M ? lo[c] : -1;
     const bool keep = l >= 0;
-    const unsigned long long votes = __ballot(keep);
-    const unsigned rank = (unsigned)__popcll(votes & ((1ull << lane) - 1ull));
-    if (lane == 0) s_cnt[p & 1][wave] = (unsigned)__popcll(votes);
-    __syncthreads();
-    unsigned before = 0, total = 0;
-    for (int w = 0; w < RE_THREADS / 64; ++w) {
-      const unsigned n = s_cnt[p & 1][w];
-      if (w < wave) before += n;
-      total += n;
+    const int64_t s = block_compact_slot<RE_THREADS>(keep, p, at);
+    if (keep && s < K) {  // acceptance stops at K: the output holds exactly E + 2 K columns
+      const int64_t h = (int64_t)hi[c];
+      out0[E + s] = (int64_t)l, out1[E + s] = h;
+      out0[E + K + s] = h, out1[E + K + s] = (int64_t)l;
     }
-    if (keep) {
-      const int64_t s = at + before + rank;
-      if (s < K) {  // acceptance stops at K: the output holds exactly E + 2 K columns
-        const int64_t h = (int64_t)hi[c];
-        out0[E + s] = (int64_t)l, out1[E + s] = h;
-        out0[E + K + s] = h, out1[E + K + s] = (int64_t)l;
-      }
-    }
-    at += total;
   }
 }
 
@@ -236,17 +207,17 @@ static const char* re_plan(int64_t N, int64_t E, int64_t K, int64_t M, RePlan* p
   int64_t cap = 256;
   while (cap < need + need / 2 + 1) cap <<= 1;  // load factor <= 2/3
   if (cap > RE_CAPMAX) return "E + K + M too large for the pair table (2^31 slots)";
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  WsCarver c;
   p->M = M, p->cap = cap, p->nb = (M + RE_BLOCK - 1) / RE_BLOCK;
-  p->header = 0;  // cnt[RE_ROUNDS + 1] int64
-  p->keys = 256;
+  p->header = c.take(256);  // cnt[RE_ROUNDS + 1] int64
+  p->keys = c.take((size_t)cap * 12);
   p->vals = p->keys + (size_t)cap * 8;  // directly behind the keys: one memset of all-ones bytes sets both
-  p->lo = al(p->vals + (size_t)cap * 4);
-  p->hi = al(p->lo + (size_t)M * 4);
-  p->slot = al(p->hi + (size_t)M * 4);
-  p->blkcnt = al(p->slot + (size_t)M * 4);
-  p->offs = al(p->blkcnt + (size_t)p->nb * 4);
-  p->total = al(p->offs + (size_t)p->nb * 8);
+  p->lo = c.take((size_t)M * 4);
+  p->hi = c.take((size_t)M * 4);
+  p->slot = c.take((size_t)M * 4);
+  p->blkcnt = c.take((size_t)p->nb * 4);
+  p->offs = c.take((size_t)p->nb * 8);
+  p->total = align256(c.end);
   return nullptr;
 }
 
@@ -260,17 +231,12 @@ extern "C" int mgn_randedge(const int64_t* row0, const int64_t* row1, int64_t E,
                             uint32_t offset, int64_t* out0, int64_t* out1, int* flags, void* ws, size_t ws_bytes, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   RePlan p;
-  if (const char* why = re_plan(N, E, K, M, &p)) {
-    snprintf(g_rerr, sizeof(g_rerr), "mgn_randedge: %s", why);
-    return 1;
-  }
-  if (!row0 || !row1) return rfail(1, "mgn_randedge: row0 / row1 must not be null");
-  if (!out0 || !out1) return rfail(1, "mgn_randedge: out0 / out1 must not be null");
-  if (!flags) return rfail(1, "mgn_randedge: flags must not be null");
-  const size_t base = ((size_t)ws + 255) & ~(size_t)255;
-  if (!ws || ws_bytes < (base - (size_t)ws) + p.total)
-    return rfail(1, "mgn_randedge: workspace (ws_bytes) too small: see mgn_randedge_workspace_bytes");
-  char* w = (char*)base;
+  if (const char* why = re_plan(N, E, K, M, &p)) return failf(1, "mgn_randedge", why);
+  if (!row0 || !row1) return fail(1, "mgn_randedge: row0 / row1 must not be null");
+  if (!out0 || !out1) return fail(1, "mgn_randedge: out0 / out1 must not be null");
+  if (!flags) return fail(1, "mgn_randedge: flags must not be null");
+  char* w = ws_base(ws, ws_bytes, p.total);
+  if (!w) return fail(1, "mgn_randedge: workspace (ws_bytes) too small: see mgn_randedge_workspace_bytes");
   int64_t* cnt = (int64_t*)(w + p.header);
   unsigned long long* keys = (unsigned long long*)(w + p.keys);
   uint32_t* vals = (uint32_t*)(w + p.vals);
@@ -279,11 +245,11 @@ extern "C" int mgn_randedge(const int64_t* row0, const int64_t* row1, int64_t E,
   int64_t* offs = (int64_t*)(w + p.offs);
   const uint64_t mask = (uint64_t)p.cap - 1;
   const long Ml = (long)p.M;
-  if (hipMemsetAsync(cnt, 0, 256, s) != hipSuccess) return rfail(2, "mgn_randedge: memset");
-  if (hipMemsetAsync(keys, 0xff, (size_t)p.cap * 12, s) != hipSuccess) return rfail(2, "mgn_randedge: memset");
+  if (hipMemsetAsync(cnt, 0, 256, s) != hipSuccess) return fail(2, "mgn_randedge: memset");
+  if (hipMemsetAsync(keys, 0xff, (size_t)p.cap * 12, s) != hipSuccess) return fail(2, "mgn_randedge: memset");
   // every slot of the new columns holds an in-range id also where the rounds come up short
-  if (hipMemsetAsync(out0 + E, 0, (size_t)K * 16, s) != hipSuccess) return rfail(2, "mgn_randedge: memset");
-  if (hipMemsetAsync(out1 + E, 0, (size_t)K * 16, s) != hipSuccess) return rfail(2, "mgn_randedge: memset");
+  if (hipMemsetAsync(out0 + E, 0, (size_t)K * 16, s) != hipSuccess) return fail(2, "mgn_randedge: memset");
+  if (hipMemsetAsync(out1 + E, 0, (size_t)K * 16, s) != hipSuccess) return fail(2, "mgn_randedge: memset");
   hipLaunchKernelGGL(k_re_input, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, s, row0, row1, (long)E, (long)N, out0, out1, keys, vals, mask,
                      flags);
   const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32) ^ RE_KEY_TWEAK;
@@ -296,10 +262,5 @@ extern "C" int mgn_randedge(const int64_t* row0, const int64_t* row1, int64_t E,
     hipLaunchKernelGGL(k_re_fill, dim3((unsigned)p.nb), dim3(RE_THREADS), 0, s, r, Ml, (long)K, (long)E, (const int64_t*)cnt,
                        (const int32_t*)lo, (const int32_t*)hi, (const int64_t*)offs, out0, out1);
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    snprintf(g_rerr, sizeof(g_rerr), "mgn_randedge: %s", hipGetErrorString(e));
-    return 2;
-  }
-  return 0;
+  return check_launch("mgn_randedge");
 }

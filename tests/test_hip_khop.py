@@ -82,6 +82,49 @@ def test_khop_path_and_empty(dev):
     assert got.shape == (2, 0)
 
 
+def _pairs(*cols):
+    """the distinct (row0, row1) columns in ascending order: what coalescing leaves"""
+    p = np.concatenate([np.asarray(c, dtype=np.int64).reshape(2, -1) for c in cols], axis=1)
+    return np.unique(p, axis=1) if p.shape[1] else p
+
+
+@pytest.mark.parametrize("case", ["none dropped", "all dropped", "mixed"])
+def test_shared_edge_key_convention_on_five_nodes(dev, case):
+    """The three callers of the shared sort + unique (khop_edges, faces_to_edges, add_world_edges) against numpy.unique on
+    (row0, row1) pairs: a dropped pair gets the all-ones key, all of them collapse into one trailing key, and that one is left
+    out -- with no such key in the list, with nothing else in it, and with both kinds."""
+    N = 5
+    ei, face = {"none dropped": ([[0, 1, 2, 3, 1, 4], [1, 2, 3, 4, 2, 0]], [[0, 1, 2], [1, 2, 3], [2, 3, 4]]),
+                "all dropped": ([[1, 2, 2, 4], [1, 2, 2, 4]], [[0, 1, 4], [0, 1, 4], [0, 1, 4]]),
+                "mixed": ([[0, 3, 1, 2, 3, 1, 4], [1, 3, 2, 3, 4, 2, 4]], [[0, 1, 2, 4], [0, 2, 2, 4], [1, 2, 3, 4]])}[case]
+    ei, face = np.array(ei, dtype=np.int64), np.array(face, dtype=np.int64)
+
+    # khop_edges, two hops: walks of one or two edges, self loops carry nothing, (i, i) is never a pair
+    e = ei[:, ei[0] != ei[1]]
+    two = [(a, d) for a, b in e.T for c, d in e.T if b == c and a != d]
+    got = P.khop_edges(torch.from_numpy(ei).to(dev), N, 2).cpu().numpy()
+    assert got.dtype == np.int64 and np.array_equal(got, _pairs(e, np.array(two, dtype=np.int64).reshape(-1, 2).T))
+
+    # faces_to_edges: every pair of distinct corners of a face, both ways
+    both = [(f[a], f[b]) for f in face.T for a in range(3) for b in range(3) if f[a] != f[b]]
+    got = P.faces_to_edges(torch.from_numpy(face).to(dev), N).cpu().numpy()
+    assert got.dtype == np.int64 and np.array_equal(got, _pairs(np.array(both, dtype=np.int64).reshape(-1, 2).T))
+
+    # add_world_edges: the input in both directions (self loops stay) plus the one OBSTACLE - NORMAL pair in reach, (4, 0).
+    # Its key list always ends in unused all-ones slots; "none dropped" leaves the single spare one, "all dropped" only those.
+    x = np.zeros((N, 3), dtype=np.float32)                                   # [world x, world y, node type]
+    x[:, 0] = np.arange(N)
+    wei, world = ei, np.zeros((2, 0), dtype=np.int64)
+    if case == "all dropped":
+        wei = np.zeros((2, 0), dtype=np.int64)
+    if case == "mixed":
+        x[4] = (0.01, 0.0, 1.0)
+        world = np.array([[4, 0], [0, 4]])
+    got = P.add_world_edges(torch.from_numpy(x).to(dev), torch.from_numpy(wei).to(dev), 0, 2, 2, radius=0.03,
+                            max_world_pairs=0 if case == "none dropped" else None).cpu().numpy()
+    assert got.dtype == np.int64 and np.array_equal(got, _pairs(wei, wei[::-1], world))
+
+
 @pytest.mark.parametrize("k", [2, 3])
 def test_khop_both_paths_in_one_call(dev, k):
     """a mesh plus a hub with capacity + 1 leaves: rows of the on-chip path and rows of the bitmap path in one result"""

@@ -67,6 +67,27 @@ def test_candidate_count_boundaries(dev, M):
         _check(ei, N, 1.0, dev, seed=3, offset=1, M=M)                      # K = 600: M = 255 .. 257 need three rounds
 
 
+def test_compaction_block_plus_one_every_candidate_kept_and_an_empty_block(dev):
+    """M = 2049 is one compaction block plus one candidate.  Every candidate kept: a ring of 2049 among 10^6 nodes, the draws
+    distinct, loop-free and unoccupied (asserted), K = M.  No candidate kept: the sparse regime leaves three quarters of the
+    pairs free, so no draw rejects all M candidates; the workgroup that keeps nothing is the second one, whose only candidate
+    (index 2048) repeats an earlier one or an edge (asserted)."""
+    N, ei = 1000003, ring(2049)
+    a, b = RR.draw(N, 2049, 0, 11, 0)
+    code = np.minimum(a, b) * N + np.maximum(a, b)
+    assert (a != b).all() and np.unique(code).size == 2049 and not np.isin(code, RR.occupied_codes(ei, N)).any()
+    assert RR.num_pairs(ei.shape[1], 1.0) == 2049
+    want = _check(ei, N, 1.0, dev, seed=11, M=2049)
+    assert np.array_equal(want[:, 4098:4098 + 2049], np.stack([np.minimum(a, b), np.maximum(a, b)]))   # all of them, in draw order
+
+    N, ei = 300, ring(300, chords=(7,))
+    a, b = RR.draw(N, 2049, 0, 26, 0)
+    code = np.minimum(a, b) * N + np.maximum(a, b)
+    earlier = code[:2048][a[:2048] != b[:2048]]
+    assert a[2048] == b[2048] or np.isin(code[2048], RR.occupied_codes(ei, N)) or np.isin(code[2048], earlier)
+    _check(ei, N, 1.0, dev, seed=26, M=2049)                                # K = 600
+
+
 def test_several_compaction_blocks_all_written(dev):
     N, E = 5000, 12000
     ei = R.random_graph(N, E, 4).numpy()

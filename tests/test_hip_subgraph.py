@@ -61,6 +61,15 @@ def test_workgroup_boundaries(dev):
         assert want.shape[1] == where.stop - where.start
 
 
+def test_one_block_plus_one_edge_all_kept_and_none_kept(dev):
+    B, N = _capi.lib().mgn_subgraph_block_edges(), 257
+    ei = np.random.default_rng(4).integers(0, N, size=(2, B + 1))
+    assert np.array_equal(_check(np.arange(N), ei, N, dev), ei)               # every edge kept: both workgroups full
+    subset = np.arange(0, N, 3)
+    out_nodes = np.setdiff1d(np.arange(N), subset)
+    assert _check(subset, out_nodes[ei % out_nodes.size], N, dev).shape == (2, 0)   # no edge kept, in either workgroup
+
+
 def test_degenerate_sets(dev):
     N = 300
     ei = R.random_graph(N, 900, 5).numpy()

@@ -123,6 +123,8 @@ def test_randedge_symbols_declared_exported_and_prototyped():
     assert any(s.endswith("mgn_philox.inc") for s in _capi.DEPS)           # the shared generator is part of the source hash
     mk = open(os.path.join(REPO, "graph-physics_amd", "csrc", "Makefile")).read()
     assert "mgn_randedge.hip" in mk and "mgn_philox.inc" in mk
+    for inc in ("mgn_host.inc", "mgn_graphprim.inc"):                       # the shared scaffolding and edge primitives too
+        assert any(s.endswith(inc) for s in _capi.DEPS) and inc in mk, inc
     assert lib.mgn_version() == _capi.EXPECTED_VERSION == 136              # additive change: the ABI number stays
 
 

@@ -202,8 +202,9 @@ class GatherJob(C.Structure):
                 ("ld_dst", C.c_int64), ("src_rows", C.c_int64)]
 
 
-#: every symbol include/mgn_hip.h declares: name -> (restype, argtypes)
-SYMBOLS = {
+#: every symbol include/mgn_hip.h declares, name -> (restype, argtypes), grouped by the translation unit csrc/mgn_<unit>.hip that
+#: defines it; each unit reports through its own error text (the last entry of its group), which is how `check` finds the channel
+UNITS = {"kernels": {
     "mgn_version": (C.c_int, []),
     "mgn_last_error": (C.c_char_p, []),
     "mgn_csr_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
@@ -229,6 +230,7 @@ SYMBOLS = {
     "mgn_debug_occupancy": (C.c_int, [C.POINTER(C.c_int)]),
     "mgn_transpose_blocks": (C.c_int, [C.c_int, C.POINTER(TBlock), C.c_int, C.c_void_p]),
     "mgn_wpack": (C.c_int, [C.c_int, C.POINTER(WpackBlock), C.c_void_p]),
+}, "prep": {
     "mgn_faces_to_edges_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
     "mgn_faces_to_edges": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -264,6 +266,7 @@ SYMBOLS = {
     "mgn_morton_order_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "mgn_morton_order": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "mgn_prep_last_error": (C.c_char_p, []),
+}, "attn": {
     "mgn_sparse_attn_fwd": (C.c_int, [C.c_void_p] * 5 + [C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mgn_sparse_attn_bwd": (C.c_int, [C.c_void_p] * 11 + [C.c_int64, C.c_int64, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]),
     "mgn_sparse_attn_fwd_b16": (C.c_int, [C.c_void_p] * 5 + [C.c_int64, C.c_int, C.c_int] + [C.c_void_p] * 4),
@@ -275,6 +278,7 @@ SYMBOLS = {
     "mgn_head_axis_attn_fwd": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_int, C.c_int] + [C.c_void_p] * 3),
     "mgn_head_axis_attn_bwd": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_int, C.c_int] + [C.c_void_p] * 4),
     "mgn_attn_last_error": (C.c_char_p, []),
+}, "dense": {
     "mgn_linear_fwd": (C.c_int, [C.POINTER(LinearArgs), C.c_void_p]),
     "mgn_linear_accepts_transposed": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int]),
     "mgn_rownorm2_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int64,
@@ -285,18 +289,21 @@ SYMBOLS = {
     "mgn_rownorm_bwd": (C.c_int, [C.c_void_p, C.POINTER(RownormPhase), C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_int64, C.c_void_p,
                                   C.c_void_p, C.c_size_t, C.c_void_p]),
     "mgn_dense_last_error": (C.c_char_p, []),
+}, "loss": {
     "mgn_loss_fd_geometry": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mgn_loss_ls_geometry": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_int64] + [C.c_void_p] * 6),
     "mgn_loss_workspace_bytes": (C.c_size_t, []),
     "mgn_loss_fwd": (C.c_int, [C.POINTER(LossArgs), C.c_void_p]),
     "mgn_loss_bwd": (C.c_int, [C.POINTER(LossArgs)] + [C.c_void_p] * 5),
     "mgn_loss_last_error": (C.c_char_p, []),
+}, "khop": {
     "mgn_khop_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
     "mgn_khop_row_capacity": (C.c_int, []),
     "mgn_khop_count": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                  C.c_void_p, C.c_size_t, C.c_void_p]),
     "mgn_khop_fill": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "mgn_khop_last_error": (C.c_char_p, []),
+}, "subgraph": {
     "mgn_subgraph_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
     "mgn_subgraph_block_edges": (C.c_int, []),
     "mgn_subgraph_count": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p,
@@ -304,11 +311,13 @@ SYMBOLS = {
     "mgn_subgraph_fill": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "mgn_gather_rows_batch": (C.c_int, [C.c_int, C.POINTER(GatherJob), C.c_void_p]),
     "mgn_subgraph_last_error": (C.c_char_p, []),
+}, "randedge": {
     "mgn_randedge_default_candidates": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64]),
     "mgn_randedge_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
     "mgn_randedge": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p,
                                C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "mgn_randedge_last_error": (C.c_char_p, []),
+}, "knn": {
     "mgn_knn_max_k": (C.c_int, []),
     "mgn_knn_tile_points": (C.c_int, []),
     "mgn_knn_search": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
@@ -318,7 +327,9 @@ SYMBOLS = {
     "mgn_knn_interp_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p,
                                      C.c_void_p]),
     "mgn_knn_last_error": (C.c_char_p, []),
-}
+}}
+SYMBOLS = {name: sig for group in UNITS.values() for name, sig in group.items()}
+_UNIT_OF = {name: unit for unit, group in UNITS.items() for name in group}
 
 _lib = None
 _lock = threading.Lock()
@@ -432,11 +443,14 @@ def lib():
 
 def check(rc: int, what: str, prep: bool = False, attn: bool = False, dense: bool = False, loss: bool = False, khop: bool = False,
           subgraph: bool = False, randedge: bool = False, knn: bool = False):
-    """Raise on a non-zero return code with the message of the translation unit the call lives in: the flag that is set names
-    it (mgn_<flag>_last_error; of several the last in the signature wins), none means mgn_kernels.hip (mgn_last_error)."""
+    """Raise on a non-zero return code with the message of the translation unit that defines the entry point ``what`` (UNITS).
+    The flags count only where ``what`` is no symbol name: the one that is set names the unit (mgn_<flag>_last_error; of several
+    the last in the signature wins), none means mgn_kernels.hip (mgn_last_error)."""
     if rc != 0:
-        flags = locals()
-        units = [u for u in ("prep", "attn", "dense", "loss", "khop", "subgraph", "randedge", "knn") if flags[u]]
-        fn = getattr(lib(), f"mgn_{units[-1]}_last_error" if units else "mgn_last_error")
+        unit = _UNIT_OF.get(what)
+        if unit is None:
+            flags = locals()
+            unit = ([u for u in UNITS if flags.get(u)] or ["kernels"])[-1]
+        fn = getattr(lib(), "mgn_last_error" if unit == "kernels" else f"mgn_{unit}_last_error")
         msg = fn().decode("utf-8", "replace")
         raise RuntimeError(f"{what} failed (code {rc}): {msg}")

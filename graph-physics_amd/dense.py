@@ -13,6 +13,7 @@ from typing import Optional
 import torch
 
 from . import _capi, ops
+from ._launch import call, workspace
 
 ACT_NONE = -1
 ACT_IDS = {None: ACT_NONE, "none": ACT_NONE, "relu": 0, "silu": 1, "gelu": 2}
@@ -56,9 +57,7 @@ def linear_launch(x, W, b=None, x2=None, W2=None, b2=None, norm_scale=None, act:
         a.norm_scale_outer, a.inv_outer_out = norm_outer[0].data_ptr(), ops._ptr(norm_outer[1])
     if gate_bwd is not None:   # (Z1, Z2, out2): the gated product's backward as the epilogue -- out = dZ1, out2 = dZ2
         a.gb_z1, a.gb_z2, a.out2 = gate_bwd[0].data_ptr(), gate_bwd[1].data_ptr(), gate_bwd[2].data_ptr()
-    with torch.cuda.device(x.device):
-        rc = _capi.lib().mgn_linear_fwd(C.byref(a), ops._stream(x.device))
-    _capi.check(rc, "mgn_linear_fwd", dense=True)
+    call("mgn_linear_fwd", x.device, C.byref(a))
     return out
 
 
@@ -145,9 +144,7 @@ class DenseFn(torch.autograd.Function):
         if act != ACT_NONE or W2 is not None:
             dZ1 = torch.empty(M, N, **f)
             dZ2 = torch.empty(M, N, **f) if W2 is not None else None
-            with torch.cuda.device(dev):
-                rc = L.mgn_act_gate_bwd(dy.data_ptr(), Z1.data_ptr(), ops._ptr(Z2), M, N, act, prec, dZ1.data_ptr(), ops._ptr(dZ2), ops._stream(dev))
-            _capi.check(rc, "mgn_act_gate_bwd", dense=True)
+            call("mgn_act_gate_bwd", dev, dy.data_ptr(), Z1.data_ptr(), ops._ptr(Z2), M, N, act, prec, dZ1.data_ptr(), ops._ptr(dZ2))
         else:
             dZ1, dZ2 = dy, None
         # ---- input gradient: dn = dZ1 W (+ dZ2 W2) -- the same launch with the transposed weight
@@ -170,11 +167,9 @@ class DenseFn(torch.autograd.Function):
                 if d_pass is not None:   # the gradient of the rows handed on (pass_x): added inside the norm backward
                     arr[0].acc = d_pass.data_ptr()
                 dscale = torch.empty(K, **f)
-                ws = torch.empty(max(L.mgn_rownorm_bwd_workspace_bytes(K), 16), dtype=torch.uint8, device=dev)
-                with torch.cuda.device(dev):
-                    rc = L.mgn_rownorm_bwd(dn.data_ptr(), arr, nph, inv.data_ptr(), norm_scale.data_ptr(), ops.EPS, M, dscale.data_ptr(),
-                                           ws.data_ptr(), ws.numel(), ops._stream(dev))
-                _capi.check(rc, "mgn_rownorm_bwd", dense=True)
+                ws = workspace(L.mgn_rownorm_bwd_workspace_bytes(K), dev)
+                call("mgn_rownorm_bwd", dev, dn.data_ptr(), arr, nph, inv.data_ptr(), norm_scale.data_ptr(), ops.EPS, M, dscale.data_ptr(),
+                     ws.data_ptr(), ws.numel())
             else:
                 rows, k0 = [], 0
                 for p in range(3):
@@ -351,12 +346,9 @@ class GatedMlpResidualFn(torch.autograd.Function):
 
         # both norms backward in one pass; dx = dy (the residual) + the norm path
         dx, ds_io = torch.empty(M, K, **f), torch.empty(2 * K, **f)
-        ws = torch.empty(max(L.mgn_rownorm_bwd_workspace_bytes(2 * K), 16), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            rc = L.mgn_rownorm2_bwd(dn.data_ptr(), x.data_ptr(), int(x.stride(0)), K, inv_o.data_ptr(), s_outer.data_ptr(), inv_i.data_ptr(),
-                                    s_inner.data_ptr(), ops.EPS, M, dy.data_ptr(), dx.data_ptr(), ds_io.data_ptr(), ws.data_ptr(), ws.numel(),
-                                    ops._stream(dev))
-        _capi.check(rc, "mgn_rownorm2_bwd", dense=True)
+        ws = workspace(L.mgn_rownorm_bwd_workspace_bytes(2 * K), dev)
+        call("mgn_rownorm2_bwd", dev, dn.data_ptr(), x.data_ptr(), int(x.stride(0)), K, inv_o.data_ptr(), s_outer.data_ptr(), inv_i.data_ptr(),
+             s_inner.data_ptr(), ops.EPS, M, dy.data_ptr(), dx.data_ptr(), ds_io.data_ptr(), ws.data_ptr(), ws.numel())
         ds_inner, ds_outer = ds_io[:K], ds_io[K:]
         return dx, ds_outer, ds_inner, dW1, db1, dW2, db2, dW3, db3, None, None
 
@@ -398,10 +390,7 @@ class RMSNormFn(torch.autograd.Function):
         M, K = x2d.shape
         y = torch.empty(M, K, dtype=torch.float32, device=x.device)
         inv = torch.empty(M, dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            rc = _capi.lib().mgn_rownorm_fwd(x2d.data_ptr(), int(x2d.stride(0)), K, scale.data_ptr(), ops.EPS, M, y.data_ptr(), inv.data_ptr(),
-                                             ops._stream(x.device))
-        _capi.check(rc, "mgn_rownorm_fwd", dense=True)
+        call("mgn_rownorm_fwd", x.device, x2d.data_ptr(), int(x2d.stride(0)), K, scale.data_ptr(), ops.EPS, M, y.data_ptr(), inv.data_ptr())
         ctx.save_for_backward(x2d, scale, inv)
         ctx.shape = shape
         return y.reshape(shape)
@@ -416,13 +405,11 @@ class RMSNormFn(torch.autograd.Function):
         dscale = torch.empty(K, dtype=torch.float32, device=dev) if M > 0 else torch.zeros(K, dtype=torch.float32, device=dev)
         if M > 0:
             L = _capi.lib()
-            ws = torch.empty(max(L.mgn_rownorm_bwd_workspace_bytes(K), 16), dtype=torch.uint8, device=dev)
+            ws = workspace(L.mgn_rownorm_bwd_workspace_bytes(K), dev)
             arr = (_capi.RownormPhase * 1)()
             arr[0].x, arr[0].ldx, arr[0].K, arr[0].idx, arr[0].dx, arr[0].lddx = x.data_ptr(), int(x.stride(0)), K, None, dx.data_ptr(), K
-            with torch.cuda.device(dev):
-                rc = L.mgn_rownorm_bwd(dy.data_ptr(), arr, 1, inv.data_ptr(), scale.data_ptr(), ops.EPS, M, dscale.data_ptr(), ws.data_ptr(),
-                                       ws.numel(), ops._stream(dev))
-            _capi.check(rc, "mgn_rownorm_bwd", dense=True)
+            call("mgn_rownorm_bwd", dev, dy.data_ptr(), arr, 1, inv.data_ptr(), scale.data_ptr(), ops.EPS, M, dscale.data_ptr(), ws.data_ptr(),
+                 ws.numel())
         return dx.reshape(ctx.shape), dscale
 
 

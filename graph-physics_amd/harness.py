@@ -24,6 +24,7 @@ from .nodetype import NodeType
 from .parse_parameters import get_gradient_method, get_loss, get_model, get_simulator, matrix_precision_from_config
 from .losses import L2Loss, LossGeometry, MultiLoss
 from . import ops as _ops
+from ._launch import call, stream_object
 
 
 def lr_factor(last_epoch: int, warmup: int, max_iters: int, min_lr_factor: float = 0.001) -> float:
@@ -41,7 +42,6 @@ class _MaskedMseFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, out, tgt, node_type, types):
         import ctypes as C
-        from . import _capi
         out = out.float() if out.dtype != torch.float32 else out
         tgt = tgt.float() if tgt.dtype != torch.float32 else tgt
         node_type = node_type.float() if node_type.dtype != torch.float32 else node_type
@@ -57,11 +57,8 @@ class _MaskedMseFn(torch.autograd.Function):
         loss, inv = torch.empty((), dtype=torch.float32, device=dev), scratch[513]
         tarr = (C.c_float * len(types))(*[float(t) for t in types])
         ldty = int(node_type.stride(0)) if N > 0 else 1
-        with torch.cuda.device(dev):
-            rc = _capi.lib().mgn_masked_mse_fwd(out.data_ptr(), int(out.stride(0)), tgt.data_ptr(), int(tgt.stride(0)), node_type.data_ptr(), ldty,
-                                                N, O, tarr, len(types), scratch.data_ptr(), loss.data_ptr(), inv.data_ptr(),
-                                                torch.cuda.current_stream(dev).cuda_stream)
-        _capi.check(rc, "mgn_masked_mse_fwd", prep=True)
+        call("mgn_masked_mse_fwd", dev, out.data_ptr(), int(out.stride(0)), tgt.data_ptr(), int(tgt.stride(0)), node_type.data_ptr(), ldty,
+             N, O, tarr, len(types), scratch.data_ptr(), loss.data_ptr(), inv.data_ptr())
         ctx.save_for_backward(out, tgt, node_type, scratch)
         ctx.types = tuple(float(t) for t in types)
         return loss
@@ -69,7 +66,6 @@ class _MaskedMseFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         import ctypes as C
-        from . import _capi
         out, tgt, node_type, scratch = ctx.saved_tensors
         N, O = int(out.shape[0]), int(out.shape[1])
         dev = out.device
@@ -77,11 +73,8 @@ class _MaskedMseFn(torch.autograd.Function):
         d_out = torch.empty(N, O, dtype=torch.float32, device=dev)
         tarr = (C.c_float * len(ctx.types))(*ctx.types)
         ldty = int(node_type.stride(0)) if N > 0 else 1
-        with torch.cuda.device(dev):
-            rc = _capi.lib().mgn_masked_mse_bwd(out.data_ptr(), int(out.stride(0)), tgt.data_ptr(), int(tgt.stride(0)), node_type.data_ptr(), ldty,
-                                                N, O, tarr, len(ctx.types), scratch[513].data_ptr(), g.data_ptr(), d_out.data_ptr(),
-                                                torch.cuda.current_stream(dev).cuda_stream)
-        _capi.check(rc, "mgn_masked_mse_bwd", prep=True)
+        call("mgn_masked_mse_bwd", dev, out.data_ptr(), int(out.stride(0)), tgt.data_ptr(), int(tgt.stride(0)), node_type.data_ptr(), ldty,
+             N, O, tarr, len(ctx.types), scratch[513].data_ptr(), g.data_ptr(), d_out.data_ptr())
         return d_out, None, None, None
 
 
@@ -163,23 +156,21 @@ class FusedClipAdamW:
         import os as _os
         key = tuple((arr[i].p, arr[i].m, arr[i].v, arr[i].n) for i in range(len(live)))
         tb = L.mgn_clip_adamw_table_bytes(len(live), arr) if _os.environ.get("MGN_OPT_NO_TABLE") is None else 0
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            if tb > 0:
-                if self._table_key != key:
+        if tb > 0:
+            if self._table_key != key:
+                with torch.cuda.device(self.device):
                     if torch.cuda.is_current_stream_capturing():
                         raise RuntimeError("FusedClipAdamW: the parameter table must be built by an eager step before the capture")
                     self._table = torch.empty(tb, dtype=torch.uint8, device=self.device)
-                    C.check(L.mgn_clip_adamw_table(len(live), arr, self._table.data_ptr(), tb), "mgn_clip_adamw_table", prep=True)
-                    self._table_key = key
-                rc = L.mgn_clip_adamw_t(len(live), arr, self._table.data_ptr(), float(self.max_norm), self.lr_t.data_ptr(),
-                                        self.step_t.data_ptr(), float(self.betas[0]), float(self.betas[1]), float(self.eps),
-                                        float(self.weight_decay), self.norm_t.data_ptr(), self._ws.data_ptr(), self._ws.numel(), stream)
-            else:
-                rc = L.mgn_clip_adamw(len(live), arr, float(self.max_norm), self.lr_t.data_ptr(), self.step_t.data_ptr(),
-                                      float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.weight_decay),
-                                      self.norm_t.data_ptr(), self._ws.data_ptr(), self._ws.numel(), stream)
-        C.check(rc, "mgn_clip_adamw", prep=True)
+                    C.check(L.mgn_clip_adamw_table(len(live), arr, self._table.data_ptr(), tb), "mgn_clip_adamw_table")
+                self._table_key = key
+            call("mgn_clip_adamw_t", self.device, len(live), arr, self._table.data_ptr(), float(self.max_norm), self.lr_t.data_ptr(),
+                 self.step_t.data_ptr(), float(self.betas[0]), float(self.betas[1]), float(self.eps),
+                 float(self.weight_decay), self.norm_t.data_ptr(), self._ws.data_ptr(), self._ws.numel())
+        else:
+            call("mgn_clip_adamw", self.device, len(live), arr, float(self.max_norm), self.lr_t.data_ptr(), self.step_t.data_ptr(),
+                 float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.weight_decay),
+                 self.norm_t.data_ptr(), self._ws.data_ptr(), self._ws.numel())
 
 
 class Engine:
@@ -324,13 +315,13 @@ class Engine:
             return loss.detach(), gn
 
         side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
+        side.wait_stream(stream_object(dev))
         with torch.cuda.stream(side):
             for _ in range(warmup):
                 self._lr_t.fill_(self.learning_rate * lr_factor(self.step_count, self.warmup, self.num_steps))
                 body()
                 self.step_count += 1
-        torch.cuda.current_stream(dev).wait_stream(side)
+        stream_object(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
@@ -390,11 +381,11 @@ class Engine:
             return pred
 
         side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
+        side.wait_stream(stream_object(dev))
         with torch.cuda.stream(side):
             for _ in range(max(1, warmup)):
                 body()
-        torch.cuda.current_stream(dev).wait_stream(side)
+        stream_object(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):

@@ -14,9 +14,10 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _capi, dense, ops
+from . import dense, ops
+from ._launch import call, ptr as _ptr
 from .mesh import Graph
-from .ops import _ptr, _require_device, _stream
+from .ops import _require_device
 from .preprocess import _knn_search, _knn_segments, knn_graph
 
 #: input widths of one ``mgn_linear_fwd`` launch (csrc/mgn_dense.hip).  The backward runs the same launch on dZ [M, d_out], so
@@ -51,9 +52,7 @@ class KnnInterpolateFn(torch.autograd.Function):
             raise ValueError("knn_interpolate: x needs at least one column")
         a = torch.empty(ny, k, dtype=torch.float32, device=x.device)
         out = torch.empty(ny, Fw, dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            rc = _capi.lib().mgn_knn_interp_fwd(_ptr(x), nx, Fw, _ptr(idx), _ptr(d2), ny, k, _ptr(a), _ptr(out), _stream(x.device))
-        _capi.check(rc, "mgn_knn_interp_fwd", knn=True)
+        call("mgn_knn_interp_fwd", x.device, _ptr(x), nx, Fw, _ptr(idx), _ptr(d2), ny, k, _ptr(a), _ptr(out))
         ctx.save_for_backward(idx, a)
         ctx.shape = (nx, Fw)
         return out
@@ -69,9 +68,7 @@ class KnnInterpolateFn(torch.autograd.Function):
         key = torch.where(idx < 0, torch.full_like(idx, nx), idx).reshape(-1)
         rowptr, perm = ops.csr_build(key, nx + 1)
         dx = torch.empty(nx, Fw, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = _capi.lib().mgn_knn_interp_bwd(_ptr(dy), _ptr(a), _ptr(rowptr), _ptr(perm), nx, ny, k, Fw, _ptr(dx), _stream(dev))
-        _capi.check(rc, "mgn_knn_interp_bwd", knn=True)
+        call("mgn_knn_interp_bwd", dev, _ptr(dy), _ptr(a), _ptr(rowptr), _ptr(perm), nx, ny, k, Fw, _ptr(dx))
         return dx, None, None
 
 

@@ -24,6 +24,7 @@ from typing import Optional, Sequence
 import torch
 from torch.nn.modules.loss import _Loss
 
+from ._launch import call
 from .nodetype import PREDICTED
 
 GRADIENT_METHODS = ("finite_diff", "least_squares")
@@ -114,14 +115,10 @@ class LossGeometry:
         self.rowptr[1:] = torch.cumsum(torch.bincount(rows, minlength=N), 0)
         nnz = int(rows.numel())
         if kernels:
-            from . import _capi
             self.coef = torch.empty(nnz, self.D, dtype=torch.float32, device=dev)
             self.inv = torch.empty(N, dtype=torch.float32, device=dev)
-            with torch.cuda.device(dev):
-                rc = _capi.lib().mgn_loss_fd_geometry(self.rowptr.data_ptr(), self.col.data_ptr(), self.self_loop.data_ptr(),
-                                                      self.pos.data_ptr(), self.D, N, self.coef.data_ptr(), self.inv.data_ptr(),
-                                                      torch.cuda.current_stream(dev).cuda_stream)
-            _capi.check(rc, "mgn_loss_fd_geometry", loss=True)
+            call("mgn_loss_fd_geometry", dev, self.rowptr.data_ptr(), self.col.data_ptr(), self.self_loop.data_ptr(),
+                 self.pos.data_ptr(), self.D, N, self.coef.data_ptr(), self.inv.data_ptr())
         else:
             p = self.pos.double()
             dx = p[cols] - p[rows]
@@ -152,15 +149,11 @@ class LossGeometry:
         self.nptr[1:] = torch.cumsum(torch.bincount(flat, minlength=N), 0)
         self.corner_node = flat   # torch path: node of every (e, k)
         if kernels:
-            from . import _capi
             self.cv = torch.empty(M, K, D, dtype=torch.float32, device=dev)
             self.inv = torch.empty(N, dtype=torch.float32, device=dev)
             vol = torch.empty(max(M, 1), dtype=torch.float64, device=dev)
-            with torch.cuda.device(dev):
-                rc = _capi.lib().mgn_loss_ls_geometry(self.elems.data_ptr(), M, K, self.pos.data_ptr(), D, N, self.nptr.data_ptr(),
-                                                      self.nent.data_ptr(), self.cv.data_ptr(), vol.data_ptr(), self.inv.data_ptr(),
-                                                      torch.cuda.current_stream(dev).cuda_stream)
-            _capi.check(rc, "mgn_loss_ls_geometry", loss=True)
+            call("mgn_loss_ls_geometry", dev, self.elems.data_ptr(), M, K, self.pos.data_ptr(), D, N, self.nptr.data_ptr(),
+                 self.nent.data_ptr(), self.cv.data_ptr(), vol.data_ptr(), self.inv.data_ptr())
         else:
             P = self.pos.double()[elems]               # [M, K, D]
             A = P[:, 1:, :] - P[:, :1, :]              # [M, S, D]
@@ -300,9 +293,7 @@ def _launch_fwd(net_out, target, node_type, u_out, u_tgt, geom, kinds, weights, 
         if g_out is not None:
             a.g_out = g_out.data_ptr()
             keep.append(g_out)
-    with torch.cuda.device(dev):
-        rc = L.mgn_loss_fwd(C.byref(a), torch.cuda.current_stream(dev).cuda_stream)
-    _capi.check(rc, "mgn_loss_fwd", loss=True)
+    call("mgn_loss_fwd", dev, C.byref(a))
     return a, keep, terms, total
 
 
@@ -335,7 +326,6 @@ class _FusedLossFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g, _g_terms):
-        from . import _capi
         N, O, F = ctx.shape
         dev = ctx.dev
         g = g.float().reshape(1).contiguous()
@@ -346,11 +336,8 @@ class _FusedLossFn(torch.autograd.Function):
         if need_u and ctx.geom.method == "least_squares":
             dge = torch.empty(max(ctx.geom.M, 1), F, ctx.geom.D, dtype=torch.float32, device=dev)
         if need_net or need_u:
-            with torch.cuda.device(dev):
-                rc = _capi.lib().mgn_loss_bwd(C.byref(ctx.args), g.data_ptr(), d_net.data_ptr() if need_net else None,
-                                              d_u.data_ptr() if need_u else None, dge.data_ptr() if dge is not None else None,
-                                              torch.cuda.current_stream(dev).cuda_stream)
-            _capi.check(rc, "mgn_loss_bwd", loss=True)
+            call("mgn_loss_bwd", dev, C.byref(ctx.args), g.data_ptr(), d_net.data_ptr() if need_net else None,
+                 d_u.data_ptr() if need_u else None, dge.data_ptr() if dge is not None else None)
         if ctx.needs_input_grad[0] and d_net is None:
             d_net = torch.zeros(N, O, dtype=torch.float32, device=dev)
         return d_net, None, None, d_u, None, None, None, None, None

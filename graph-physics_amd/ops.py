@@ -14,6 +14,7 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 
 from . import _capi
+from ._launch import call, ptr as _ptr, stream as _stream, stream_object, workspace
 
 EPS = 1e-8  # RMSNorm epsilon of the reference (layers.py:80)
 #: matrix path of the H = 128 kernels: split-bf16 (bf16x3 operands, 6 MFMA terms, fp32-grade
@@ -40,22 +41,6 @@ def set_matrix_precision(p: str) -> None:
 def get_matrix_precision() -> str:
     return _matrix_precision
 SUPPORTED_H = (16, 32, 64, 128)
-
-
-def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
-    return None if t is None else t.data_ptr()
-
-
-_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-
-
-def _stream(dev: torch.device) -> int:
-    """the hipStream_t of torch's current stream on ``dev`` (what every launch of the engine is queued on).  The raw query is one C call;
-    building a ``torch.cuda.Stream`` object for it costs ~5 us, 60-90 times per training step"""
-    if _raw_stream is not None:
-        idx = dev.index
-        return _raw_stream(torch.cuda.current_device() if idx is None else idx)
-    return torch.cuda.current_stream(dev).cuda_stream
 
 
 def _require_device(*ts: torch.Tensor):
@@ -118,10 +103,8 @@ def morton_order(pos: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     L = _capi.lib()
     order = torch.empty(N, dtype=torch.int32, device=dev)
     rank = torch.empty(N, dtype=torch.int32, device=dev)
-    ws = torch.empty(max(L.mgn_morton_order_workspace_bytes(N), 16), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.mgn_morton_order(_ptr(pos), int(pos.shape[1]), D, N, _ptr(order), _ptr(rank), _ptr(ws), ws.numel(), _stream(dev))
-    _capi.check(rc, "mgn_morton_order", prep=True)
+    ws = workspace(L.mgn_morton_order_workspace_bytes(N), dev)
+    call("mgn_morton_order", dev, _ptr(pos), int(pos.shape[1]), D, N, _ptr(order), _ptr(rank), _ptr(ws), ws.numel())
     return order, rank
 
 
@@ -190,7 +173,7 @@ class Topology:
         self.rowptr_dst, self.rowptr_src = torch.empty(N + 1, **i32), torch.empty(N + 1, **i32)
         self.perm_dst, self.perm_src = torch.empty(E, **i32), torch.empty(E, **i32)
         self.src_s, self.dst_s = torch.empty(E, **i32), torch.empty(E, **i32)
-        ws = torch.empty(max(L.mgn_topology_workspace_bytes(E, N), 16), dtype=torch.uint8, device=dev)
+        ws = workspace(L.mgn_topology_workspace_bytes(E, N), dev)
         self._inv = None
         self._pending = None
         self._error = None   # sticky: a topology whose build reported stray indices raises on EVERY resolve / use
@@ -198,25 +181,21 @@ class Topology:
         self.hub_dst = self.hub_src = None
         if lazy:
             flags = torch.zeros(4, **i32)
+            call("mgn_topology_build_async", dev, ei[0].data_ptr(), ei[1].data_ptr(), E, N, _ptr(self.rowptr_dst), _ptr(self.perm_dst),
+                 _ptr(self.src_s), _ptr(self.dst_s), _ptr(self.rowptr_src), _ptr(self.perm_src), _ptr(flags), _ptr(ws), ws.numel())
             with torch.cuda.device(dev):
-                rc = L.mgn_topology_build_async(ei[0].data_ptr(), ei[1].data_ptr(), E, N, _ptr(self.rowptr_dst), _ptr(self.perm_dst),
-                                                _ptr(self.src_s), _ptr(self.dst_s), _ptr(self.rowptr_src), _ptr(self.perm_src),
-                                                _ptr(flags), _ptr(ws), ws.numel(), _stream(dev))
-                _capi.check(rc, "mgn_topology_build_async")
                 host = torch.empty(4, dtype=torch.int32, pin_memory=True)
                 host.copy_(flags, non_blocking=True)
                 ev = torch.cuda.Event()
-                ev.record(torch.cuda.current_stream(dev))
+                ev.record(stream_object(dev))
             self._pending = (ev, host, flags, ws)   # flags / ws stay referenced until the copy has run
             self.max_in_degree = self.max_out_degree = None
             return
         mx = (C.c_int32 * 2)()
-        with torch.cuda.device(dev):
-            rc = L.mgn_topology_build(ei[0].data_ptr(), ei[1].data_ptr(), E, N, _ptr(self.rowptr_dst), _ptr(self.perm_dst), _ptr(self.src_s),
-                                      _ptr(self.dst_s), _ptr(self.rowptr_src), _ptr(self.perm_src), mx, _ptr(ws), ws.numel(), _stream(dev))
+        rc = call("mgn_topology_build", dev, ei[0].data_ptr(), ei[1].data_ptr(), E, N, _ptr(self.rowptr_dst), _ptr(self.perm_dst),
+                  _ptr(self.src_s), _ptr(self.dst_s), _ptr(self.rowptr_src), _ptr(self.perm_src), mx, _ptr(ws), ws.numel(), accept=(3,))
         if rc == 3:
             raise IndexError(f"edge_index has entries outside [0, {N})")
-        _capi.check(rc, "mgn_topology_build")
         self._set_degrees(int(mx[0]), int(mx[1]))
 
     def _set_degrees(self, din: int, dout: int):
@@ -356,13 +335,10 @@ def csr_build(key: torch.Tensor, n: int) -> Tuple[torch.Tensor, torch.Tensor]:
     dev = key.device
     rowptr = torch.empty(n + 1, dtype=torch.int32, device=dev)
     perm = torch.empty(E, dtype=torch.int32, device=dev)
-    nbytes = L.mgn_csr_workspace_bytes(E, n)
-    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.mgn_csr_build(_ptr(key), E, n, _ptr(rowptr), _ptr(perm), _ptr(ws), ws.numel(), _stream(dev))
+    ws = workspace(L.mgn_csr_workspace_bytes(E, n), dev)
+    rc = call("mgn_csr_build", dev, _ptr(key), E, n, _ptr(rowptr), _ptr(perm), _ptr(ws), ws.numel(), accept=(3,))
     if rc == 3:
         raise IndexError(f"edge_index has entries outside [0, {n})")
-    _capi.check(rc, "mgn_csr_build")
     return rowptr, perm
 
 
@@ -373,27 +349,20 @@ def segsum(src: torch.Tensor, rowptr: torch.Tensor, perm: Optional[torch.Tensor]
     H = src.shape[1]
     if out is None:
         out = torch.empty(n, H, dtype=torch.float32, device=src.device)
-    with torch.cuda.device(src.device):
-        rc = _capi.lib().mgn_segsum(_ptr(src), _ptr(rowptr), _ptr(perm), _ptr(out), n, H, _stream(src.device))
-    _capi.check(rc, "mgn_segsum")
+    call("mgn_segsum", src.device, _ptr(src), _ptr(rowptr), _ptr(perm), _ptr(out), n, H)
     return out
 
 
 def seg_fix(rowptr: torch.Tensor, part: torch.Tensor, out: torch.Tensor):
     """second stage of the segment sum fused into ``mlp_fwd(seg=...)``"""
-    with torch.cuda.device(out.device):
-        rc = _capi.lib().mgn_seg_fix(_ptr(rowptr), _ptr(part), _ptr(out), rowptr.numel() - 1, _stream(out.device))
-    _capi.check(rc, "mgn_seg_fix")
+    call("mgn_seg_fix", out.device, _ptr(rowptr), _ptr(part), _ptr(out), rowptr.numel() - 1)
 
 
 def segsum2(src: torch.Tensor, rowptr0, perm0, out0, rowptr1, perm1, out1):
     """two segment sums of the same source rows in one launch (H = 128)"""
     n = rowptr0.numel() - 1
-    fn = _capi.lib().mgn_segsum2_b16 if src.dtype == torch.bfloat16 else _capi.lib().mgn_segsum2   # (two-byte rows: dZ[0] of precision 3)
-    with torch.cuda.device(src.device):
-        rc = fn(_ptr(src), _ptr(rowptr0), _ptr(perm0), _ptr(out0), _ptr(rowptr1), _ptr(perm1), _ptr(out1),
-                                     n, src.shape[1], _stream(src.device))
-    _capi.check(rc, "mgn_segsum2")
+    name = "mgn_segsum2_b16" if src.dtype == torch.bfloat16 else "mgn_segsum2"   # (two-byte rows: dZ[0] of precision 3)
+    call(name, src.device, _ptr(src), _ptr(rowptr0), _ptr(perm0), _ptr(out0), _ptr(rowptr1), _ptr(perm1), _ptr(out1), n, src.shape[1])
 
 
 # ----------------------------------------------------------------- raw launches
@@ -442,10 +411,7 @@ def mlp_fwd(M: int, H: int, phases: Sequence[Tuple[torch.Tensor, Optional[torch.
     if saveZ is not None:
         for l, t in enumerate(saveZ):
             a.saveZ[l] = _ptr(t)
-    dev = out.device
-    with torch.cuda.device(dev):
-        rc = _capi.lib().mgn_mlp_fwd(C.byref(a), _stream(dev))
-    _capi.check(rc, "mgn_mlp_fwd")
+    call("mgn_mlp_fwd", out.device, C.byref(a))
 
 
 def mlp_bwd(M: int, H: int, NL: int, dOut: torch.Tensor, dOut2, idx2, out_w: int, U, R, scale,
@@ -493,15 +459,12 @@ def mlp_bwd(M: int, H: int, NL: int, dOut: torch.Tensor, dOut2, idx2, out_w: int
             a.front_src[p_] = _ptr(t)
         a.front_resid, a.front_out = _ptr(fres), _ptr(fout)
     dev = dOut.device
-    nbytes = L.mgn_mlp_bwd_workspace_bytes(M, H, NL)
-    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    ws = workspace(L.mgn_mlp_bwd_workspace_bytes(M, H, NL), dev)
     a.red_ws, a.red_ws_bytes = _ptr(ws), ws.numel()
     if defer is not None:  # column sums finished later, many launches at once (colred_batch)
         a.defer_reduce = 1
         defer.append((ws, M, H, NL, out_w, len(din), list(db), dscale if scale is not None else None))
-    with torch.cuda.device(dev):
-        rc = L.mgn_mlp_bwd(C.byref(a), _stream(dev))
-    _capi.check(rc, "mgn_mlp_bwd")
+    call("mgn_mlp_bwd", dev, C.byref(a))
 
 
 _fused_ws: dict = {}
@@ -525,15 +488,13 @@ def edge_bwd_fused(E: int, dOut, dAgg, idx, U, R, scale, X: Sequence[torch.Tenso
         a.Ms[l] = _ptr(Ms[l])
     a.dIn, a.dZ0, a.dscale = _ptr(dIn), _ptr(dZ0), _ptr(dscale)
     dev = dOut.device
-    key = (dev.type, dev.index, torch.cuda.current_stream(dev).cuda_stream)
+    key = (dev.type, dev.index, _stream(dev))
     ws = _fused_ws.get(key)   # 68 MB of per-workgroup partials, re-used by every round (launches of one stream are ordered)
     if ws is None:
         ws = torch.empty(L.mgn_edge_bwd_fused_workspace_bytes(), dtype=torch.uint8, device=dev)
         _fused_ws[key] = ws
     a.ws, a.ws_bytes, a.precision = _ptr(ws), ws.numel(), precision
-    with torch.cuda.device(dev):
-        rc = L.mgn_edge_bwd_fused(C.byref(a), _stream(dev))
-    _capi.check(rc, "mgn_edge_bwd_fused")
+    call("mgn_edge_bwd_fused", dev, C.byref(a))
 
 
 def colred_batch(deferred: list, dev):
@@ -546,9 +507,7 @@ def colred_batch(deferred: list, dev):
         for l in range(NL):
             arr[i].db[l] = _ptr(db[l])
         arr[i].dscale = _ptr(dscale)
-    with torch.cuda.device(dev):
-        rc = _capi.lib().mgn_colred_batch(len(deferred), arr, _stream(dev))
-    _capi.check(rc, "mgn_colred_batch")
+    call("mgn_colred_batch", dev, len(deferred), arr)
     deferred.clear()
 
 
@@ -567,11 +526,8 @@ def wgrad(jobs, dev, precision: int = 0):
             arr[j].M = A.shape[0]
             arr[j].lda, arr[j].ldb, arr[j].ldw = lda, ldb, ldw
             arr[j].nja, arr[j].nkb, arr[j].kw = nja, nkb, kw
-        nbytes = L.mgn_wgrad_workspace_bytes(len(chunk), arr)
-        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            rc = L.mgn_wgrad_p(len(chunk), arr, _ptr(ws), ws.numel(), precision, _stream(dev))
-        _capi.check(rc, "mgn_wgrad")
+        ws = workspace(L.mgn_wgrad_workspace_bytes(len(chunk), arr), dev)
+        call("mgn_wgrad_p", dev, len(chunk), arr, _ptr(ws), ws.numel(), precision)
 
 
 def wpack(blocks: Sequence[Tuple[int, int, bool, int]], dev):
@@ -582,9 +538,7 @@ def wpack(blocks: Sequence[Tuple[int, int, bool, int]], dev):
     arr = (_capi.WpackBlock * len(blocks))()
     for i, (src, ld, tr, dst) in enumerate(blocks):
         arr[i].src, arr[i].ld_src, arr[i].transpose, arr[i].dst = src, ld, int(bool(tr)), dst
-    with torch.cuda.device(dev):
-        rc = _capi.lib().mgn_wpack(len(blocks), arr, _stream(dev))
-    _capi.check(rc, "mgn_wpack")
+    call("mgn_wpack", dev, len(blocks), arr)
 
 
 def transpose_blocks(blocks: Sequence[Tuple[int, int, int, int]], H: int, dev):
@@ -594,9 +548,7 @@ def transpose_blocks(blocks: Sequence[Tuple[int, int, int, int]], H: int, dev):
     arr = (_capi.TBlock * len(blocks))()
     for i, (src, lds, dst, ldd) in enumerate(blocks):
         arr[i].src, arr[i].ld_src, arr[i].dst, arr[i].ld_dst = src, lds, dst, ldd
-    with torch.cuda.device(dev):
-        rc = _capi.lib().mgn_transpose_blocks(len(blocks), arr, H, _stream(dev))
-    _capi.check(rc, "mgn_transpose_blocks")
+    call("mgn_transpose_blocks", dev, len(blocks), arr, H)
 
 
 # ------------------------------------------------------------ small row kernels
@@ -605,51 +557,37 @@ def gather_rows(src: torch.Tensor, idx: torch.Tensor, out: Optional[torch.Tensor
     n, H = int(idx.numel()), int(src.shape[1])
     if out is None:
         out = torch.empty(n, H, dtype=torch.float32, device=src.device)
-    with torch.cuda.device(src.device):
-        rc = _capi.lib().mgn_gather_rows(_ptr(src), _ptr(idx), n, H, _ptr(out), _stream(src.device))
-    _capi.check(rc, "mgn_gather_rows", prep=True)
+    call("mgn_gather_rows", src.device, _ptr(src), _ptr(idx), n, H, _ptr(out))
     return out
 
 
 def halo_unpack_add(rows: torch.Tensor, nodes: torch.Tensor, rowptr: torch.Tensor, perm: torch.Tensor, dst: torch.Tensor):
     """dst[nodes[j]] += sum of rows[perm[rowptr[j]:rowptr[j+1]]] in ascending order (atomics-free)."""
-    with torch.cuda.device(dst.device):
-        rc = _capi.lib().mgn_halo_unpack_add(_ptr(rows), _ptr(nodes), _ptr(rowptr), _ptr(perm), int(nodes.numel()), int(dst.shape[1]),
-                                             _ptr(dst), _stream(dst.device))
-    _capi.check(rc, "mgn_halo_unpack_add", prep=True)
+    call("mgn_halo_unpack_add", dst.device, _ptr(rows), _ptr(nodes), _ptr(rowptr), _ptr(perm), int(nodes.numel()), int(dst.shape[1]),
+         _ptr(dst))
 
 
 def gate_fwd(G, phi, gate_pos, agg, gate_out, agg_out):
-    with torch.cuda.device(agg.device):
-        rc = _capi.lib().mgn_gate_fwd(_ptr(G), _ptr(phi), _ptr(gate_pos), _ptr(agg), int(agg.shape[0]), int(agg.shape[1]),
-                                      _ptr(gate_out), _ptr(agg_out), _stream(agg.device))
-    _capi.check(rc, "mgn_gate_fwd", prep=True)
+    call("mgn_gate_fwd", agg.device, _ptr(G), _ptr(phi), _ptr(gate_pos), _ptr(agg), int(agg.shape[0]), int(agg.shape[1]),
+         _ptr(gate_out), _ptr(agg_out))
 
 
 def gate_bwd(dAggG, agg, gate, dAgg, dG):
-    with torch.cuda.device(agg.device):
-        rc = _capi.lib().mgn_gate_bwd(_ptr(dAggG), _ptr(agg), _ptr(gate), int(agg.shape[0]), int(agg.shape[1]), _ptr(dAgg), _ptr(dG),
-                                      _stream(agg.device))
-    _capi.check(rc, "mgn_gate_bwd", prep=True)
+    call("mgn_gate_bwd", agg.device, _ptr(dAggG), _ptr(agg), _ptr(gate), int(agg.shape[0]), int(agg.shape[1]), _ptr(dAgg), _ptr(dG))
 
 
 def rope_gather(x, pos, inv_freq, topo: "Topology", axes: int, out):
     """out[k] = RoPE(x[src[k]], pos[src[k]] - pos[dst[k]]) for the dst-sorted edges (layers.py:1020-1026,1104-1149)."""
-    with torch.cuda.device(x.device):
-        rc = _capi.lib().mgn_rope_gather(_ptr(x), _ptr(pos), int(pos.shape[1]), _ptr(inv_freq), int(inv_freq.numel()), axes,
-                                         _ptr(topo.src_s), _ptr(topo.dst_s), topo.E, int(x.shape[1]), _ptr(out), _stream(x.device))
-    _capi.check(rc, "mgn_rope_gather", prep=True)
+    call("mgn_rope_gather", x.device, _ptr(x), _ptr(pos), int(pos.shape[1]), _ptr(inv_freq), int(inv_freq.numel()), axes,
+         _ptr(topo.src_s), _ptr(topo.dst_s), topo.E, int(x.shape[1]), _ptr(out))
 
 
 def rope_scatter(T, pos, inv_freq, topo: "Topology", axes: int, resid, out):
     """out[j] = resid[j] + sum_{k: src[k]=j} RoPE^T(T[k]) (the gradient of rope_gather wrt x), in the
     fixed order of the src-grouped CSR."""
     n = int(out.shape[0])
-    with torch.cuda.device(T.device):
-        rc = _capi.lib().mgn_rope_scatter(_ptr(T), _ptr(pos), int(pos.shape[1]), _ptr(inv_freq), int(inv_freq.numel()), axes,
-                                          _ptr(topo.src_s), _ptr(topo.dst_s), _ptr(topo.rowptr_src), _ptr(topo.perm_src), n,
-                                          int(T.shape[1]), _ptr(resid), _ptr(out), _stream(T.device))
-    _capi.check(rc, "mgn_rope_scatter", prep=True)
+    call("mgn_rope_scatter", T.device, _ptr(T), _ptr(pos), int(pos.shape[1]), _ptr(inv_freq), int(inv_freq.numel()), axes,
+         _ptr(topo.src_s), _ptr(topo.dst_s), _ptr(topo.rowptr_src), _ptr(topo.perm_src), n, int(T.shape[1]), _ptr(resid), _ptr(out))
 
 
 # ``ctx.needs_input_grad`` mirrors ``tensor.requires_grad`` even under ``torch.no_grad()``, and
@@ -1284,7 +1222,7 @@ class ProcessorFunction(torch.autograd.Function):
             side = _side_stream(dev)
             wsets = [(dZn, dZe, Sd, Ss), ([mk(Nn, H, **f) for _ in range(NL)], [torch.empty_like(t) for t in dZe], mk(N, H, **f), mk(N, H, **f))]
             wdone = [None, None]
-            main = torch.cuda.current_stream(dev)
+            main = stream_object(dev)
         dx_buf, de_buf = [mk(Nn, H, **f), mk(Nn, H, **f)], [mk(E, H, **f), mk(E, H, **f)]
         # [r5] Weight gradients of SEVERAL rounds in one launch (up to MAX_WGRAD_JOBS jobs = 4 rounds of the default block): a
         # round's dW depends on nothing the rest of the backward pass waits for, so its jobs can wait until a launch is full -- one

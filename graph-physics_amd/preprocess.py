@@ -10,7 +10,8 @@ from typing import Optional
 import torch
 
 from . import _capi
-from .ops import _ptr, _require_device, _stream
+from ._launch import call, ptr as _ptr, stream_object, workspace
+from .ops import _require_device
 
 
 def faces_to_edges(face: torch.Tensor, num_nodes: int) -> torch.Tensor:
@@ -27,13 +28,11 @@ def faces_to_edges(face: torch.Tensor, num_nodes: int) -> torch.Tensor:
     cap = F * K * (K - 1)
     out = torch.empty(2, max(cap, 1), dtype=torch.int64, device=dev)
     n = torch.zeros(1, dtype=torch.int64, device=dev)
-    ws = torch.empty(max(L.mgn_faces_to_edges_workspace_bytes(F, K), 16), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.mgn_faces_to_edges(_ptr(f), K, F, int(num_nodes), out[0].data_ptr(), out[1].data_ptr(), _ptr(n),
-                                  _ptr(ws), ws.numel(), _stream(dev))
+    ws = workspace(L.mgn_faces_to_edges_workspace_bytes(F, K), dev)
+    rc = call("mgn_faces_to_edges", dev, _ptr(f), K, F, int(num_nodes), out[0].data_ptr(), out[1].data_ptr(), _ptr(n),
+              _ptr(ws), ws.numel(), accept=(3,))
     if rc == 3:
         raise IndexError(f"face has corners outside [0, {num_nodes})")
-    _capi.check(rc, "mgn_faces_to_edges", prep=True)
     E = int(n.item())
     return out[:, :E].contiguous()
 
@@ -49,9 +48,7 @@ def edge_features(pos: torch.Tensor, edge_index: torch.Tensor, out: Optional[tor
     E = int(ei.shape[1])
     if out is None:
         out = torch.empty(E, D + 1, dtype=torch.float32, device=pos.device)
-    with torch.cuda.device(pos.device):
-        rc = _capi.lib().mgn_edge_features(_ptr(p), D, ei[0].data_ptr(), ei[1].data_ptr(), E, _ptr(out), _stream(pos.device))
-    _capi.check(rc, "mgn_edge_features", prep=True)
+    call("mgn_edge_features", pos.device, _ptr(p), D, ei[0].data_ptr(), ei[1].data_ptr(), E, _ptr(out))
     return out
 
 
@@ -72,16 +69,14 @@ def add_world_edges(x: torch.Tensor, edge_index: torch.Tensor, world_pos_index_s
     mw = int(max_world_pairs if max_world_pairs is not None else 16 * N)
     out = torch.empty(2, 2 * E + 2 * mw + 1, dtype=torch.int64, device=dev)
     n = torch.zeros(1, dtype=torch.int64, device=dev)
-    ws = torch.empty(max(L.mgn_world_edges_workspace_bytes(E, mw), 16), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.mgn_add_world_edges(_ptr(xx), int(xx.shape[1]), int(world_pos_index_start), D, int(node_type_index), N, float(radius),
-                                   ei[0].data_ptr(), ei[1].data_ptr(), E, mw, out[0].data_ptr(), out[1].data_ptr(), _ptr(n),
-                                   _ptr(ws), ws.numel(), _stream(dev))
+    ws = workspace(L.mgn_world_edges_workspace_bytes(E, mw), dev)
+    rc = call("mgn_add_world_edges", dev, _ptr(xx), int(xx.shape[1]), int(world_pos_index_start), D, int(node_type_index), N, float(radius),
+              ei[0].data_ptr(), ei[1].data_ptr(), E, mw, out[0].data_ptr(), out[1].data_ptr(), _ptr(n), _ptr(ws), ws.numel(),
+              accept=(3, 4))
     if rc == 3:
         raise IndexError(f"edge_index has entries outside [0, {N})")
     if rc == 4:
         raise RuntimeError("more world-edge pairs than max_world_pairs; pass a larger bound")
-    _capi.check(rc, "mgn_add_world_edges", prep=True)
     return out[:, :int(n.item())].contiguous()
 
 
@@ -96,18 +91,15 @@ def _khop(edge_index: torch.Tensor, num_nodes: int, num_hops: int):
     ei = edge_index.to(torch.int64).contiguous()
     N, E = int(num_nodes), int(ei.shape[1])
     nbytes = L.mgn_khop_workspace_bytes(N, E)
-    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    ws = workspace(nbytes, dev)
     n_out, n_ovf = C.c_int64(0), C.c_int64(0)
-    with torch.cuda.device(dev):
-        rc = L.mgn_khop_count(ei[0].data_ptr(), ei[1].data_ptr(), E, N, int(num_hops), C.byref(n_out), C.byref(n_ovf),
-                              _ptr(ws), nbytes, _stream(dev))
-        if rc == 3:
-            raise IndexError(f"edge_index has entries outside [0, {N})")
-        _capi.check(rc, "mgn_khop_count", khop=True)
-        out = torch.empty(2, n_out.value, dtype=torch.int64, device=dev)
-        if n_out.value > 0:
-            rc = L.mgn_khop_fill(_ptr(ws), nbytes, N, int(num_hops), out[0].data_ptr(), out[1].data_ptr(), n_out.value, _stream(dev))
-            _capi.check(rc, "mgn_khop_fill", khop=True)
+    rc = call("mgn_khop_count", dev, ei[0].data_ptr(), ei[1].data_ptr(), E, N, int(num_hops), C.byref(n_out), C.byref(n_ovf),
+              _ptr(ws), nbytes, accept=(3,))
+    if rc == 3:
+        raise IndexError(f"edge_index has entries outside [0, {N})")
+    out = torch.empty(2, n_out.value, dtype=torch.int64, device=dev)
+    if n_out.value > 0:
+        call("mgn_khop_fill", dev, _ptr(ws), nbytes, N, int(num_hops), out[0].data_ptr(), out[1].data_ptr(), n_out.value)
     return out, n_ovf.value
 
 
@@ -184,9 +176,7 @@ def gather_rows_batch(sources, indices):
         keep += [w_src, w_dst, idx]
         n += 1
     if n:
-        with torch.cuda.device(dev):
-            rc = _capi.lib().mgn_gather_rows_batch(n, jobs, _stream(dev))
-        _capi.check(rc, "mgn_gather_rows_batch", subgraph=True)
+        call("mgn_gather_rows_batch", dev, n, jobs)
     return outs
 
 
@@ -197,14 +187,12 @@ def _subgraph_count(subset: torch.Tensor, ei: torch.Tensor, N: int, ws: torch.Te
     dev = ei.device
     S, E = int(subset.numel()), int(ei.shape[1])
     n_edges = C.c_int64(0)
-    with torch.cuda.device(dev):
-        rc = _capi.lib().mgn_subgraph_count(subset.data_ptr() if S else None, S, N, ei[0].data_ptr() if E else None,
-                                            ei[1].data_ptr() if E else None, E, C.byref(n_edges), _ptr(ws), ws.numel(), _stream(dev))
+    rc = call("mgn_subgraph_count", dev, subset.data_ptr() if S else None, S, N, ei[0].data_ptr() if E else None,
+              ei[1].data_ptr() if E else None, E, C.byref(n_edges), _ptr(ws), ws.numel(), accept=(3, 5))
     if rc == 3:
         raise IndexError(f"subset or edge_index has entries outside [0, {N})")
     if rc == 5:
         raise ValueError("subset lists a node twice")
-    _capi.check(rc, "mgn_subgraph_count", subgraph=True)
     return n_edges.value
 
 
@@ -227,10 +215,8 @@ def _subgraph_edges(subset: torch.Tensor, edge_index: torch.Tensor, num_nodes: i
     out = torch.empty(2, n, dtype=torch.int64, device=dev)
     edge_pos = torch.empty(n, dtype=torch.int64, device=dev)
     mask = torch.empty(E, dtype=torch.uint8, device=dev) if want_mask else None
-    with torch.cuda.device(dev):
-        rc = L.mgn_subgraph_fill(_ptr(ws), nbytes, E, out[0].data_ptr() if n else None, out[1].data_ptr() if n else None,
-                                 edge_pos.data_ptr() if n else None, mask.data_ptr() if want_mask and E else None, n, _stream(dev))
-    _capi.check(rc, "mgn_subgraph_fill", subgraph=True)
+    call("mgn_subgraph_fill", dev, _ptr(ws), nbytes, E, out[0].data_ptr() if n else None, out[1].data_ptr() if n else None,
+         edge_pos.data_ptr() if n else None, mask.data_ptr() if want_mask and E else None, n)
     return out, edge_pos, (mask.view(torch.bool) if want_mask else None)
 
 
@@ -365,7 +351,7 @@ _randedge_state: dict = {}   # per device index: {"flags": device int32[4], "pen
 def _randedge_raise(st, bits: int):
     """the sticky device flag has been seen: clear it (one queued memset), forget older copies of it, raise"""
     st["flags"].zero_()
-    torch.cuda.current_stream(st["flags"].device).synchronize()   # the error path may wait: later copies must not carry the bit again
+    stream_object(st["flags"].device).synchronize()   # the error path may wait: later copies must not carry the bit again
     st["pending"].clear()
     if bits & 1:
         raise IndexError("add_random_edges: edge_index has entries outside [0, num_nodes)")
@@ -470,13 +456,12 @@ def add_random_edges(edge_index: torch.Tensor, num_nodes: int, p: float, seed: i
         _randedge_check(st, wait=False)   # an earlier call's flag, if it has arrived
         out = torch.empty(2, E + 2 * K, dtype=torch.int64, device=dev)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        rc = L.mgn_randedge(ei[0].data_ptr(), ei[1].data_ptr(), E, N, K, M, int(seed) & (2 ** 64 - 1), int(offset) & 0xFFFFFFFF,
-                            out[0].data_ptr(), out[1].data_ptr(), _ptr(st["flags"]), _ptr(ws), nbytes, _stream(dev))
-        _capi.check(rc, "mgn_randedge", randedge=True)
+        call("mgn_randedge", dev, ei[0].data_ptr(), ei[1].data_ptr(), E, N, K, M, int(seed) & (2 ** 64 - 1), int(offset) & 0xFFFFFFFF,
+             out[0].data_ptr(), out[1].data_ptr(), _ptr(st["flags"]), _ptr(ws), nbytes)
         host = torch.empty(4, dtype=torch.int32, pin_memory=True)
         host.copy_(st["flags"], non_blocking=True)
         ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(dev))
+        ev.record(stream_object(dev))
         st["pending"].append((ev, host))
     return out
 
@@ -508,10 +493,8 @@ def add_noise(graph, noise_index_start, noise_index_end, noise_scale, node_type_
     n = len(noise_index_start)
     scales = [(10 * s * (1 + math.cos(t * math.pi)) if t is not None else s) for s in noise_scale]
     st, en, sc = (C.c_int * n)(*noise_index_start), (C.c_int * n)(*noise_index_end), (C.c_float * n)(*scales)
-    with torch.cuda.device(x.device):
-        rc = _capi.lib().mgn_add_noise(_ptr(x), int(x.shape[1]), int(x.shape[0]), n, st, en, sc, int(node_type_index),
-                                       int(seed) & (2 ** 64 - 1), int(offset) & 0xFFFFFFFF, _stream(x.device))
-    _capi.check(rc, "mgn_add_noise", prep=True)
+    call("mgn_add_noise", x.device, _ptr(x), int(x.shape[1]), int(x.shape[0]), n, st, en, sc, int(node_type_index),
+         int(seed) & (2 ** 64 - 1), int(offset) & 0xFFFFFFFF)
     return graph
 
 
@@ -750,10 +733,7 @@ def _knn_search(pos_x: torch.Tensor, pos_y: torch.Tensor, k: int, ptr_x: torch.T
     nx, ny, D = int(x.shape[0]), int(y.shape[0]), int(x.shape[1])
     idx = torch.empty(ny, k, dtype=torch.int64, device=dev)
     d2 = torch.empty(ny, k, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.mgn_knn_search(_ptr(x), nx, _ptr(y), ny, D, k, _ptr(ptr_x), _ptr(ptr_y), nseg, 1 if exclude_self else 0, _ptr(idx), _ptr(d2),
-                              _stream(dev))
-    _capi.check(rc, "mgn_knn_search", knn=True)
+    call("mgn_knn_search", dev, _ptr(x), nx, _ptr(y), ny, D, k, _ptr(ptr_x), _ptr(ptr_y), nseg, 1 if exclude_self else 0, _ptr(idx), _ptr(d2))
     return idx, d2
 
 

@@ -16,6 +16,7 @@ import torch
 import torch.nn as nn
 
 from . import _capi
+from ._launch import call
 from .layers import Normalizer
 from .mesh import Graph
 from .nodetype import NodeType
@@ -132,9 +133,7 @@ class Simulator(nn.Module):
         if self._ws is None or self._ws.device != dev:
             self._ws = torch.empty(L.mgn_sim_workspace_bytes(), dtype=torch.uint8, device=dev)
         import ctypes as C
-        with torch.cuda.device(dev):
-            rc = L.mgn_sim_pre(C.byref(d), self._ws.data_ptr(), self._ws.numel(), torch.cuda.current_stream(dev).cuda_stream)
-        _capi.check(rc, "mgn_sim_pre", prep=True)
+        call("mgn_sim_pre", dev, C.byref(d), self._ws.data_ptr(), self._ws.numel())
         if not self._types_checked and not torch.cuda.is_current_stream_capturing():
             self._types_checked = True  # one sync, on the first step only
             self.check_node_types()
@@ -159,13 +158,10 @@ class Simulator(nn.Module):
         no = network_output.detach().to(torch.float32).contiguous()
         nz = self._output_normalizer
         pred = torch.empty(x.shape[0], self.output_size, dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            rc = _capi.lib().mgn_sim_post(x.data_ptr(), x.shape[1], self.output_index_start, self.node_type_index,
-                                          (y.data_ptr() if y is not None else None), (y.shape[1] if y is not None else 0),
-                                          no.data_ptr(), self.output_size, nz._acc_sum.data_ptr(), nz._acc_sum_squared.data_ptr(),
-                                          nz._acc_count.data_ptr(), float(nz._std_epsilon_value), int(bool(mask_truth)), x.shape[0],
-                                          pred.data_ptr(), torch.cuda.current_stream(x.device).cuda_stream)
-        _capi.check(rc, "mgn_sim_post", prep=True)
+        call("mgn_sim_post", x.device, x.data_ptr(), x.shape[1], self.output_index_start, self.node_type_index,
+             (y.data_ptr() if y is not None else None), (y.shape[1] if y is not None else 0),
+             no.data_ptr(), self.output_size, nz._acc_sum.data_ptr(), nz._acc_sum_squared.data_ptr(),
+             nz._acc_count.data_ptr(), float(nz._std_epsilon_value), int(bool(mask_truth)), x.shape[0], pred.data_ptr())
         return pred
 
     def _get_pre_target(self, inputs) -> torch.Tensor:

@@ -22,7 +22,8 @@ from typing import Optional
 import torch
 import torch.nn as nn
 
-from . import _capi, ops
+from . import ops
+from ._launch import call
 from .dense import ACT_IDS, GatedMlpResidualFn, SigmoidGateFn, dense, rms_norm
 from .gated import build_gated_mlp
 from .layers import RMSNorm, build_mlp
@@ -90,15 +91,12 @@ class SparseAttentionFn(torch.autograd.Function):
         lse = torch.empty_like(q)
         need_raw = b16 and any(ctx.needs_input_grad[:3])
         y_raw = torch.empty_like(q) if need_raw else None     # the unrounded rows: the backward's y
-        with torch.cuda.device(q.device):
-            if b16:
-                rc = _capi.lib().mgn_sparse_attn_fwd_b16(q.data_ptr(), k.data_ptr(), v.data_ptr(), topo.rowptr.data_ptr(), topo.col.data_ptr(),
-                                                         N, H, num_heads, y.data_ptr(), lse.data_ptr(),
-                                                         y_raw.data_ptr() if need_raw else None, ops._stream(q.device))
-            else:
-                rc = _capi.lib().mgn_sparse_attn_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), topo.rowptr.data_ptr(), topo.col.data_ptr(),
-                                                     N, H, num_heads, y.data_ptr(), lse.data_ptr(), ops._stream(q.device))
-        _capi.check(rc, "mgn_sparse_attn_fwd", attn=True)
+        if b16:
+            call("mgn_sparse_attn_fwd_b16", q.device, q.data_ptr(), k.data_ptr(), v.data_ptr(), topo.rowptr.data_ptr(), topo.col.data_ptr(),
+                 N, H, num_heads, y.data_ptr(), lse.data_ptr(), y_raw.data_ptr() if need_raw else None)
+        else:
+            call("mgn_sparse_attn_fwd", q.device, q.data_ptr(), k.data_ptr(), v.data_ptr(), topo.rowptr.data_ptr(), topo.col.data_ptr(),
+                 N, H, num_heads, y.data_ptr(), lse.data_ptr())
         ctx.save_for_backward(q, k, v, y_raw if need_raw else y, lse)
         ctx.topo, ctx.num_heads, ctx.b16 = topo, num_heads, b16
         ctx.mark_non_differentiable(lse)
@@ -112,13 +110,10 @@ class SparseAttentionFn(torch.autograd.Function):
         N, H = q.shape
         dq, dk, dv = torch.empty_like(q), torch.empty_like(q), torch.empty_like(q)
         ws = torch.empty(max(2 * topo.E * nh + (N * H if ctx.b16 else 0), 1), dtype=torch.float32, device=q.device)
-        fn = _capi.lib().mgn_sparse_attn_bwd_b16 if ctx.b16 else _capi.lib().mgn_sparse_attn_bwd
-        with torch.cuda.device(q.device):
-            rc = fn(q.data_ptr(), k.data_ptr(), v.data_ptr(), y.data_ptr(), lse.data_ptr(), dy.data_ptr(),
-                    topo.rowptr.data_ptr(), topo.col.data_ptr(), topo.cptr.data_ptr(), topo.cperm.data_ptr(),
-                    topo.crow.data_ptr(), N, topo.E, H, nh, dq.data_ptr(), dk.data_ptr(), dv.data_ptr(),
-                    ws.data_ptr(), ws.numel() * 4, ops._stream(q.device))
-        _capi.check(rc, "mgn_sparse_attn_bwd", attn=True)
+        call("mgn_sparse_attn_bwd_b16" if ctx.b16 else "mgn_sparse_attn_bwd", q.device,
+             q.data_ptr(), k.data_ptr(), v.data_ptr(), y.data_ptr(), lse.data_ptr(), dy.data_ptr(),
+             topo.rowptr.data_ptr(), topo.col.data_ptr(), topo.cptr.data_ptr(), topo.cperm.data_ptr(),
+             topo.crow.data_ptr(), N, topo.E, H, nh, dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), ws.data_ptr(), ws.numel() * 4)
         return dq, dk, dv, None, None, None
 
 
@@ -158,11 +153,9 @@ class PackedAttentionFn(torch.autograd.Function):
         y, lse = torch.empty(N, H, dtype=torch.float32, device=qkv.device), torch.empty(N, H, dtype=torch.float32, device=qkv.device)
         need_raw = b16 and ctx.needs_input_grad[0]
         y_raw = torch.empty_like(y) if need_raw else None
-        with torch.cuda.device(qkv.device):
-            rc = _capi.lib().mgn_sparse_attn_fwd_s(qkv.data_ptr(), H3, kv.data_ptr(), int(kv.stride(0)), kv.data_ptr() + H * ekv, int(kv.stride(0)),
-                                                   mode, topo.rowptr.data_ptr(), topo.col.data_ptr(), N, H, num_heads, y.data_ptr(),
-                                                   lse.data_ptr(), y_raw.data_ptr() if need_raw else None, ops._stream(qkv.device))
-        _capi.check(rc, "mgn_sparse_attn_fwd_s", attn=True)
+        call("mgn_sparse_attn_fwd_s", qkv.device, qkv.data_ptr(), H3, kv.data_ptr(), int(kv.stride(0)), kv.data_ptr() + H * ekv, int(kv.stride(0)),
+             mode, topo.rowptr.data_ptr(), topo.col.data_ptr(), N, H, num_heads, y.data_ptr(), lse.data_ptr(),
+             y_raw.data_ptr() if need_raw else None)
         ctx.save_for_backward(qkv, kv if mode == 1 else qkv.new_empty(0), y_raw if need_raw else y, lse)
         ctx.topo, ctx.num_heads, ctx.b16 = topo, num_heads, mode
         return y
@@ -178,13 +171,10 @@ class PackedAttentionFn(torch.autograd.Function):
         ekv = kv.element_size()
         d = torch.empty_like(qkv)
         ws = torch.empty(max(2 * topo.E * nh + (N * H if mode == 1 else 0), 1), dtype=torch.float32, device=qkv.device)
-        with torch.cuda.device(qkv.device):
-            rc = _capi.lib().mgn_sparse_attn_bwd_s(qkv.data_ptr(), H3, kv.data_ptr(), int(kv.stride(0)), kv.data_ptr() + H * ekv, int(kv.stride(0)),
-                                                   mode, y.data_ptr(), lse.data_ptr(), dy.data_ptr(), topo.rowptr.data_ptr(),
-                                                   topo.col.data_ptr(), topo.cptr.data_ptr(), topo.cperm.data_ptr(), topo.crow.data_ptr(),
-                                                   N, topo.E, H, nh, d.data_ptr(), H3, d.data_ptr() + 4 * H, H3, d.data_ptr() + 8 * H, H3,
-                                                   ws.data_ptr(), ws.numel() * 4, ops._stream(qkv.device))
-        _capi.check(rc, "mgn_sparse_attn_bwd_s", attn=True)
+        call("mgn_sparse_attn_bwd_s", qkv.device, qkv.data_ptr(), H3, kv.data_ptr(), int(kv.stride(0)), kv.data_ptr() + H * ekv, int(kv.stride(0)),
+             mode, y.data_ptr(), lse.data_ptr(), dy.data_ptr(), topo.rowptr.data_ptr(),
+             topo.col.data_ptr(), topo.cptr.data_ptr(), topo.cperm.data_ptr(), topo.crow.data_ptr(),
+             N, topo.E, H, nh, d.data_ptr(), H3, d.data_ptr() + 4 * H, H3, d.data_ptr() + 8 * H, H3, ws.data_ptr(), ws.numel() * 4)
         return d, None, None, None
 
 
@@ -199,10 +189,7 @@ class HeadAxisAttentionFn(torch.autograd.Function):
         N, H = q.shape
         y = torch.empty_like(q)
         lse = torch.empty(N, H // num_heads, dtype=torch.float32, device=q.device)
-        with torch.cuda.device(q.device):
-            rc = _capi.lib().mgn_head_axis_attn_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), N, H, num_heads, y.data_ptr(), lse.data_ptr(),
-                                                    ops._stream(q.device))
-        _capi.check(rc, "mgn_head_axis_attn_fwd", attn=True)
+        call("mgn_head_axis_attn_fwd", q.device, q.data_ptr(), k.data_ptr(), v.data_ptr(), N, H, num_heads, y.data_ptr(), lse.data_ptr())
         ctx.save_for_backward(q, k, v, y, lse)
         ctx.num_heads = num_heads
         return y
@@ -213,10 +200,8 @@ class HeadAxisAttentionFn(torch.autograd.Function):
         dy = dy.float().contiguous()
         N, H = q.shape
         dq, dk, dv = torch.empty_like(q), torch.empty_like(q), torch.empty_like(q)
-        with torch.cuda.device(q.device):
-            rc = _capi.lib().mgn_head_axis_attn_bwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), y.data_ptr(), lse.data_ptr(), dy.data_ptr(),
-                                                    N, H, ctx.num_heads, dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), ops._stream(q.device))
-        _capi.check(rc, "mgn_head_axis_attn_bwd", attn=True)
+        call("mgn_head_axis_attn_bwd", q.device, q.data_ptr(), k.data_ptr(), v.data_ptr(), y.data_ptr(), lse.data_ptr(), dy.data_ptr(),
+             N, H, ctx.num_heads, dq.data_ptr(), dk.data_ptr(), dv.data_ptr())
         return dq, dk, dv, None
 
 
@@ -235,11 +220,8 @@ def sparse_attention(q, k, v, topo: AttnTopology, num_heads: int, return_attenti
         return y
     qd, kd = q.detach().float().contiguous(), k.detach().float().contiguous()
     attn = torch.empty(topo.E, num_heads, dtype=torch.float32, device=q.device)
-    with torch.cuda.device(q.device):
-        rc = _capi.lib().mgn_sparse_attn_weights(qd.data_ptr(), kd.data_ptr(), lse.data_ptr(), topo.rowptr.data_ptr(), topo.col.data_ptr(),
-                                                 topo.perm.data_ptr(), qd.shape[0], qd.shape[1], num_heads, attn.data_ptr(),
-                                                 ops._stream(q.device))
-    _capi.check(rc, "mgn_sparse_attn_weights", attn=True)
+    call("mgn_sparse_attn_weights", q.device, qd.data_ptr(), kd.data_ptr(), lse.data_ptr(), topo.rowptr.data_ptr(), topo.col.data_ptr(),
+         topo.perm.data_ptr(), qd.shape[0], qd.shape[1], num_heads, attn.data_ptr())
     return y, attn
 
 

@@ -2,18 +2,16 @@
 values minted from the reference (tests/golden/physics_losses.npz).  The device kernels are held to the same fixture in
 tests/test_hip_losses.py."""
 import ctypes
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import REPO, assert_close3, rel_err
+from conftest import assert_close3, rel_err
 
 import graph_physics_amd as gp
 from graph_physics_amd import losses as LS
+import capi_layout
 import loss_fixture as LF
 
 FWD_TOL = 1e-5
@@ -145,22 +143,9 @@ def test_a_self_pair_only_weighs():
 def test_loss_args_layout_matches_header(tmp_path):
     from graph_physics_amd import _capi as c
 
-    cc = shutil.which("gcc") or shutil.which("cc")
-    assert cc, "a C compiler is part of the toolchain contract"
-    lines = ["#include <stdio.h>", "#include <stddef.h>", '#include "mgn_hip.h"', "int main(void) {",
-             'printf("size %zu\\n", sizeof(mgn_loss_args));']
-    for fld, _ in c.LossArgs._fields_:
-        lines.append(f'printf("{fld} %zu\\n", offsetof(mgn_loss_args, {fld}));')
-    lines += ['printf("MAXT %d\\n", MGN_LOSS_MAX_TERMS);', "return 0; }"]
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "layout"
-    subprocess.run([cc, "-I", os.path.join(REPO, "include"), "-o", str(exe), str(src)], check=True)
-    got = dict(l.split() for l in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
-    assert int(got["size"]) == ctypes.sizeof(c.LossArgs)
-    for fld, _ in c.LossArgs._fields_:
-        assert int(got[fld]) == getattr(c.LossArgs, fld).offset, fld
-    assert int(got["MAXT"]) == c.MAX_LOSS_TERMS
+    got = capi_layout.gcc_layout(tmp_path, {"mgn_loss_args": c.LossArgs}, macros=["MGN_LOSS_MAX_TERMS"])
+    capi_layout.assert_layout(got, "mgn_loss_args", c.LossArgs)
+    assert got["MGN_LOSS_MAX_TERMS"] == c.MAX_LOSS_TERMS
     assert (LS._L2, LS._COSINE, LS._L1SMOOTH, LS._GRADIENT, LS._CONVECTION, LS._DIV_L2, LS._DIV_L1, LS._DIV_L1SMOOTH) == tuple(range(8))
 
 

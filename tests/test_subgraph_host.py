@@ -5,8 +5,6 @@ checks before any launch), the partition arithmetic of ``preprocess`` and the co
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -61,25 +59,14 @@ def test_subgraph_symbols_declared_exported_and_prototyped():
 
 
 def test_gather_job_layout_matches_header(tmp_path):
-    from conftest import REPO
+    import capi_layout
     from graph_physics_amd import _capi
 
     st = _capi.GatherJob
-    cc = shutil.which("gcc") or shutil.which("cc")
-    assert cc, "a C compiler is part of the toolchain contract"
-    lines = ["#include <stdio.h>", "#include <stddef.h>", '#include "mgn_hip.h"', "int main(void) {",
-             'printf("size %zu\\n", sizeof(mgn_gather_job));', 'printf("max %d\\n", MGN_MAX_GATHER_JOBS);']
-    lines += [f'printf("{f} %zu\\n", offsetof(mgn_gather_job, {f}));' for f, _ in st._fields_]
-    lines += ["return 0; }"]
-    src, exe = tmp_path / "layout.c", tmp_path / "layout"
-    src.write_text("\n".join(lines))
-    subprocess.run([cc, "-I", os.path.join(REPO, "include"), "-o", str(exe), str(src)], check=True)
-    got = dict(l.split() for l in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
-    assert int(got["size"]) == C.sizeof(st)
-    assert int(got["max"]) == _capi.MAX_GATHER_JOBS == 8
+    got = capi_layout.gcc_layout(tmp_path, {"mgn_gather_job": st}, macros=["MGN_MAX_GATHER_JOBS"])
+    capi_layout.assert_layout(got, "mgn_gather_job", st)
+    assert got["MGN_MAX_GATHER_JOBS"] == _capi.MAX_GATHER_JOBS == 8
     assert [f for f, _ in st._fields_] == ["src", "ld_src", "width", "idx", "rows", "dst", "ld_dst", "src_rows"]
-    for f, _ in st._fields_:
-        assert int(got[f]) == getattr(st, f).offset, f
 
 
 def test_subgraph_host_queries_need_no_gpu():

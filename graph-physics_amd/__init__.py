@@ -12,6 +12,8 @@ from .losses import (LossType, MultiLoss, L2Loss, CosineLoss, L1SmoothLoss, Grad
                      DivergenceL1Loss, DivergenceL1SmoothLoss, LossGeometry, compute_gradient)
 from .ops import set_matrix_precision, get_matrix_precision, set_node_renumbering, get_node_renumbering  # noqa: F401
 from . import preprocess  # noqa: F401
+from . import meshmask  # noqa: F401
+from .meshmask import get_masked_indexes, filter_edges, build_masked_graph, reconstruct_graph  # noqa: F401
 from .preprocess import knn, knn_graph, min_distance_to_type  # noqa: F401
 from .hierarchical_pooling import DownSampler, UpSampler, knn_interpolate  # noqa: F401
 

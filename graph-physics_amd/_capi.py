@@ -190,6 +190,7 @@ class LossArgs(C.Structure):
         ("ge_out", _f32p), ("ge_tgt", _f32p),
         ("g_out", _f32p), ("a_out", _f32p), ("bu_out", _f32p), ("b_out", _f32p), ("part", _f32p),
         ("terms", _f32p), ("total", _f32p), ("invcount", _f32p),
+        ("exclude", C.c_void_p),
     ]
 
 

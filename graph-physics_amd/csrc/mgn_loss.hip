@@ -274,7 +274,8 @@ __global__ void __launch_bounds__(256) k_loss_node_fwd(mgn_loss_args a) {
     }
     if (valid && lane == 0) {   // one lane per node from here: the terms, and what the backward needs
     const float ty = a.type[n * a.ldty];
-    const bool sel = ty == t0 || ty == t1 || ty == t2 || ty == t3;
+    // a row listed in exclude leaves every mean; its field values were still gathered by its neighbours above
+    const bool sel = (ty == t0 || ty == t1 || ty == t2 || ty == t3) && !(a.exclude != nullptr && a.exclude[n] != 0);
     if (physics && a.g_out != nullptr) {
 #pragma unroll
       for (int f = 0; f < LF; ++f)

@@ -214,6 +214,20 @@ def _mask_of(node_type: torch.Tensor, masks: Sequence[int]) -> torch.Tensor:
     return mask
 
 
+def _exclude_of(selected_indexes, n: int, device) -> Optional[torch.Tensor]:
+    """``[n]`` uint8, 1 on the rows ``selected_indexes`` lists (the reference's ``~isin(arange(n), selected_indexes)``,
+    loss.py:19-34: the rows LISTED are LEFT OUT); entries outside ``[0, n)`` and repeated entries change nothing.  ``None`` or an
+    empty tensor: ``None``.  Torch ops only, no host synchronisation."""
+    if selected_indexes is None:
+        return None
+    sel = torch.as_tensor(selected_indexes, device=device).reshape(-1).long()
+    if sel.numel() == 0:
+        return None
+    ex = torch.zeros(n + 1, dtype=torch.uint8, device=device)   # slot n swallows what is out of range
+    ex[torch.where((sel >= 0) & (sel < n), sel, torch.full_like(sel, n))] = 1
+    return ex[:n]
+
+
 def _masked_mean(err: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
     """mean over all elements of the selected rows, without a data-dependent shape"""
     e = err.reshape(err.shape[0], -1)
@@ -247,7 +261,7 @@ def _term_torch(kind: int, beta: float, out, tgt, mask, u_out, u_tgt, g_out, g_t
 
 
 # ================================================================================ the fused path
-def _launch_fwd(net_out, target, node_type, u_out, u_tgt, geom, kinds, weights, masks, g_out=None):
+def _launch_fwd(net_out, target, node_type, u_out, u_tgt, geom, kinds, weights, masks, g_out=None, exclude=None):
     """fill an ``mgn_loss_args`` and run ``mgn_loss_fwd``; returns (args, tensors kept alive, terms, total)"""
     from . import _capi
     dev = net_out.device
@@ -258,6 +272,9 @@ def _launch_fwd(net_out, target, node_type, u_out, u_tgt, geom, kinds, weights, 
     a.net_out, a.ld_out = net_out.data_ptr(), int(net_out.stride(0)) if N else O
     a.target, a.ld_tgt = target.data_ptr(), int(target.stride(0)) if N else O
     a.type, a.ldty = node_type.data_ptr(), int(node_type.stride(0)) if N else 1
+    if exclude is not None:
+        a.exclude = exclude.data_ptr()
+        keep.append(exclude)
     a.ntypes = len(masks)
     for i, t in enumerate(masks):
         a.types[i] = float(int(t))
@@ -302,7 +319,7 @@ class _FusedLossFn(torch.autograd.Function):
     fields; gradients into ``net_out`` (pointwise terms) and ``u_out`` (physics terms)"""
 
     @staticmethod
-    def forward(ctx, net_out, target, node_type, u_out, u_tgt, geom, kinds, weights, masks):
+    def forward(ctx, net_out, target, node_type, u_out, u_tgt, geom, kinds, weights, masks, exclude=None):
         f32 = lambda t: t if t.dtype == torch.float32 else t.float()   # noqa: E731
         rows = lambda t: t if t.stride(-1) == 1 else t.contiguous()    # noqa: E731
         net_out, target, node_type = rows(f32(net_out)), rows(f32(target)), f32(node_type)
@@ -315,7 +332,9 @@ class _FusedLossFn(torch.autograd.Function):
                 raise ValueError("loss: the physical fields and the geometry must describe the same nodes")
             if not 1 <= int(u_out.shape[1]) <= 4:
                 raise ValueError("loss: the physics kernels take fields of 1..4 columns")
-        a, keep, terms, total = _launch_fwd(net_out, target, node_type, u_out, u_tgt, geom, kinds, weights, masks)
+        if exclude is not None and (exclude.dtype != torch.uint8 or exclude.shape != (N,) or not exclude.is_contiguous()):
+            raise ValueError("loss: exclude must be a contiguous uint8 tensor of one entry per row")
+        a, keep, terms, total = _launch_fwd(net_out, target, node_type, u_out, u_tgt, geom, kinds, weights, masks, exclude=exclude)
         ctx.args, ctx.keep = a, keep
         ctx.shape = (N, int(net_out.shape[1]), int(u_out.shape[1]) if u_out is not None else 0)
         ctx.geom = geom if u_out is not None else None
@@ -340,15 +359,17 @@ class _FusedLossFn(torch.autograd.Function):
                  d_u.data_ptr() if need_u else None, dge.data_ptr() if dge is not None else None)
         if ctx.needs_input_grad[0] and d_net is None:
             d_net = torch.zeros(N, O, dtype=torch.float32, device=dev)
-        return d_net, None, None, d_u, None, None, None, None, None
+        return d_net, None, None, d_u, None, None, None, None, None, None
 
 
 def evaluate(kinds: Sequence[int], weights: Sequence[float], betas: Sequence[float], *, graph=None, target=None,
              network_output=None, node_type=None, masks=None, network_output_physical=None, target_physical=None,
-             gradient_method=None, network_output_gradient=None, target_gradient=None, geometry: Optional[LossGeometry] = None):
+             gradient_method=None, network_output_gradient=None, target_gradient=None, geometry: Optional[LossGeometry] = None,
+             selected_indexes=None):
     """``(sum_t w_t loss_t, [w_t loss_t])`` for the terms ``kinds``.  Device tensors go through the engine's fused kernels (every
     term in one pass); CPU tensors, ``MGN_TORCH_LOSS``, a caller-supplied gradient tensor or a ``beta`` other than 1 take the torch
-    formulas."""
+    formulas.  ``selected_indexes`` has the reference's meaning (loss.py:19-34): the rows it lists are left out of every term's
+    mean, while their field values still feed their neighbours' nodal gradients."""
     masks = tuple(int(t) for t in (masks if masks is not None else PREDICTED))
     physics = any(k >= _GRADIENT for k in kinds)
     anchor = network_output if network_output is not None else network_output_physical
@@ -368,11 +389,14 @@ def evaluate(kinds: Sequence[int], weights: Sequence[float], betas: Sequence[flo
     fused = (_use_kernels(anchor) and network_output_gradient is None and target_gradient is None and 1 <= len(masks) <= 4
              and len(kinds) <= 8 and all(float(b) == 1.0 for b in betas) and network_output.dim() == 2 and node_type.dim() == 1
              and (not physics or (network_output_physical.dim() == 2 and network_output_physical.shape[1] <= 4)))
+    exclude = _exclude_of(selected_indexes, int(node_type.shape[0]), node_type.device)
     if fused:
         total, terms = _FusedLossFn.apply(network_output, target, node_type, network_output_physical, target_physical,
-                                          geometry if physics else None, tuple(kinds), tuple(float(w) for w in weights), masks)
+                                          geometry if physics else None, tuple(kinds), tuple(float(w) for w in weights), masks, exclude)
         return total, list(terms.unbind(0))
     mask = _mask_of(node_type, masks)
+    if exclude is not None:
+        mask = torch.logical_and(mask, exclude == 0)
     g_out = g_tgt = None
     if physics:
         g_out = network_output_gradient if network_output_gradient is not None else geometry.gradient(network_output_physical)
@@ -397,15 +421,16 @@ class _Term(_Loss):
     def forward(self, graph=None, target=None, network_output=None, node_type=None, masks=None, selected_indexes=None,
                 network_output_physical=None, target_physical=None, gradient_method=None, network_output_gradient=None,
                 target_gradient=None, **kwargs) -> torch.Tensor:
-        if selected_indexes is not None:
-            raise NotImplementedError("selected_indexes is not supported (the training step never passes it)")
-        if self.kind == _L2 and network_output is not None:   # the engine's existing masked-MSE path, unchanged
+        if selected_indexes is not None and torch.as_tensor(selected_indexes).numel() == 0:
+            selected_indexes = None   # nothing listed: the call without the argument
+        if self.kind == _L2 and network_output is not None and selected_indexes is None:   # the engine's existing masked-MSE path, unchanged
             from .harness import l2_loss
             return l2_loss(network_output, target, node_type, tuple(masks) if masks is not None else PREDICTED)
         total, _ = evaluate((self.kind,), (1.0,), (self.beta,), graph=graph, target=target, network_output=network_output,
                             node_type=node_type, masks=masks, network_output_physical=network_output_physical,
                             target_physical=target_physical, gradient_method=gradient_method,
-                            network_output_gradient=network_output_gradient, target_gradient=target_gradient)
+                            network_output_gradient=network_output_gradient, target_gradient=target_gradient,
+                            selected_indexes=selected_indexes)
         return total
 
 
@@ -476,13 +501,11 @@ class MultiLoss(_Loss):
 
     def forward(self, graph=None, network_output_physical=None, target_physical=None, gradient_method=None,
                 return_all_losses: bool = False, geometry: Optional[LossGeometry] = None, **kwargs):
-        if kwargs.get("selected_indexes") is not None:
-            raise NotImplementedError("selected_indexes is not supported (the training step never passes it)")
         total, terms = evaluate([l.kind for l in self.losses], self.weights, [l.beta for l in self.losses], graph=graph,
                                 target=kwargs.get("target"), network_output=kwargs.get("network_output"),
                                 node_type=kwargs.get("node_type"), masks=kwargs.get("masks"),
                                 network_output_physical=network_output_physical, target_physical=target_physical,
-                                gradient_method=gradient_method, geometry=geometry)
+                                gradient_method=gradient_method, geometry=geometry, selected_indexes=kwargs.get("selected_indexes"))
         return (total, terms) if return_all_losses else total
 
 

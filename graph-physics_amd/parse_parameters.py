@@ -15,7 +15,8 @@ from .simulator import Simulator
 
 def get_preprocessing(param: Dict[str, Any], device: torch.device, use_edge_feature: bool = True, remove_noise: bool = False,
                       extra_node_features=None, extra_edge_features=None, use_partitioning: bool = False,
-                      num_partitions: Optional[int] = None, max_nodes_per_partition: Optional[int] = None):
+                      num_partitions: Optional[int] = None, max_nodes_per_partition: Optional[int] = None,
+                      masking_ratio: Optional[float] = None):
     """The preprocessing callable of a config (training/parse_parameters.py:24-78): reads
     ``transformations.preprocessing.noise`` / ``noise_index_start`` / ``noise_index_end``,
     ``transformations.world_pos_parameters`` and ``index.node_type_index`` and returns
@@ -38,7 +39,13 @@ def get_preprocessing(param: Dict[str, Any], device: torch.device, use_edge_feat
     part of the mesh, cut as the last step (``preprocess.build_preprocessing(partitioning=...)``), and the callable takes a
     keyword ``part``.  Naming both counts or neither is the reference's ``ValueError``.  A part carries no ``face``: a config
     whose loss section needs it (physics terms with ``gradient_method: least_squares``) is refused here with a ``ValueError``,
-    not by the first training step.  Without ``use_partitioning`` the two counts are ignored, as in the reference."""
+    not by the first training step.  Without ``use_partitioning`` the two counts are ignored, as in the reference.
+
+    ``masking_ratio`` is the reference's ``get_dataset(..., masking_ratio=...)`` argument: with a number in ``[0, 1]`` the callable
+    returns ``(graph, selected_indices)`` (``preprocess.build_preprocessing(masking_ratio=...)``; the draw comes after k-hop and the
+    random edges).  A bool, a non-number or a value outside ``[0, 1]`` is a ``ValueError``, and so is ``masking_ratio`` together with
+    ``use_partitioning`` (the reference marks the combination "not working").  The reference freezes a frame's draw while the frame
+    sits in its LRU frame cache; the engine draws per ``(seed, step)``.  ``None`` leaves the callable as it is."""
     from .preprocess import build_preprocessing
 
     prep = param.get("transformations", {}).get("preprocessing", {})
@@ -63,6 +70,13 @@ def get_preprocessing(param: Dict[str, Any], device: torch.device, use_edge_feat
     if isinstance(ratio, bool) or not isinstance(ratio, (int, float)) or not 0 <= ratio <= 1:
         raise ValueError(f"dataset.new_edges_ratio: a number in [0, 1], got {ratio!r}")
     extra = {}
+    if masking_ratio is not None:
+        from .meshmask import check_masking_ratio
+
+        extra["masking_ratio"] = check_masking_ratio(masking_ratio)
+        if use_partitioning:
+            raise ValueError("masking_ratio and use_partitioning cannot be combined (masking a partitioned sample is not supported, as "
+                             "in the reference)")
     if ratio > 0:
         if torch.device(device).type != "cuda":
             raise NotImplementedError("dataset.new_edges_ratio: random extra edges are drawn by GPU kernels only (there is no host "

@@ -527,7 +527,8 @@ def add_world_pos_features(graph, world_pos_index_start: int, world_pos_index_en
 
 def build_preprocessing(noise_parameters=None, world_pos_parameters=None, add_edges_features: bool = True,
                         extra_node_features=None, extra_edge_features=None, seed: int = 0, khop: int = 1,
-                        khop_cache: Optional[dict] = None, partitioning: Optional[dict] = None, new_edges_ratio: float = 0.0):
+                        khop_cache: Optional[dict] = None, partitioning: Optional[dict] = None, new_edges_ratio: float = 0.0,
+                        masking_ratio: Optional[float] = None):
     """Device-side ``build_preprocessing`` (preprocessing.py:380-444): the same transform ORDER as the
     reference -- extra node features, [obstacle next pos,] faces -> edges, [world edges,] edge features,
     noise inserted at position 1, extra edge features -- as one callable
@@ -559,7 +560,23 @@ def build_preprocessing(noise_parameters=None, world_pos_parameters=None, add_ed
     of the previous step is looked at with one event query (``random_edges_check``).  With ``partitioning`` the node ids stay
     cached per trajectory but the per-part plans cannot be (they hold the cut edge list, and the edges now change every
     step): every sample is cut with ``subgraph`` as the reference does and PAYS ITS ONE HOST SYNCHRONISATION per sample;
-    ``partition_cache[traj]["plans"]`` stays empty.  The default 0.0 leaves the callable as it is without the argument."""
+    ``partition_cache[traj]["plans"]`` stays empty.  The default 0.0 leaves the callable as it is without the argument.
+
+    ``masking_ratio`` in ``[0, 1]`` is the reference's ``get_dataset(..., masking_ratio=...)`` (dataset/h5_dataset.py:188,
+    235-236): every sample becomes the pair ``(graph, selected_indices)``, the indices of the nodes that stay visible
+    (``meshmask.get_masked_indexes``), drawn with ``seed`` = this callable's ``seed`` and ``offset = step`` AFTER k-hop and the
+    random edges, the reference's order (h5_dataset.py:184-188).  The graph itself is not cut: ``meshmask.build_masked_graph``
+    does that in the model.  The reference freezes a frame's draw while the frame sits in its LRU frame cache; the engine has no
+    Dataset class and draws per ``(seed, step)``.  Together with ``partitioning`` it is a ``ValueError`` (the reference marks the
+    combination "not working", h5_dataset.py:231).  ``None`` leaves the callable and its return value as they are without the
+    argument."""
+    if masking_ratio is not None:
+        from .meshmask import check_masking_ratio
+
+        check_masking_ratio(masking_ratio)
+        if partitioning is not None:
+            raise ValueError("masking_ratio and partitioning cannot be combined (masking a partitioned sample is not supported, as in "
+                             "the reference)")
     if isinstance(new_edges_ratio, bool) or not isinstance(new_edges_ratio, (int, float)) or not 0.0 <= new_edges_ratio <= 1.0:
         raise ValueError(f"new_edges_ratio must be a number in [0, 1], got {new_edges_ratio!r}")
     if partitioning is not None:
@@ -633,6 +650,15 @@ def build_preprocessing(noise_parameters=None, world_pos_parameters=None, add_ed
             graph = f(graph, step) if len(inspect.signature(f).parameters) >= 2 else f(graph)
         return graph
 
+    if masking_ratio is not None:
+        def run_masked(graph, step: int = 0):
+            from .meshmask import get_masked_indexes
+
+            graph = run(graph, step)
+            return graph, get_masked_indexes(graph, masking_ratio, seed=seed, offset=step)
+
+        run_masked.masking_ratio = masking_ratio
+        return run_masked
     if partitioning is None:
         return run
 

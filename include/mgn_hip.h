@@ -698,6 +698,9 @@ const char* mgn_dense_last_error(void);
  *   least_squares  G[n] = inv[n] * sum_{(e, k) of n} ge[e],  ge[e] = sum_k U[elems[e, k]] (x) cv[e, k]   (the one [M, F, DX] intermediate)
  * Geometry (coef / cv / inv) is computed once per mesh in fp64 and stored as fp32 (mgn_loss_*_geometry); a mesh whose positions
  * change needs a new one.  No atomics: results are bit-identical run to run.  No host synchronisation: capturable.
+ * exclude (optional, [N] bytes): a row with exclude[n] != 0 takes part in no term's mean -- the selected-row count, invcount and the
+ * row's own derivatives follow -- while its field values still feed its neighbours' nodal gradients (the reference's
+ * selected_indexes mask, utils/loss.py:19-34).  NULL: no row is excluded.  No selected row at all: 0 / 0 = nan.
  * F <= 4, DX <= 3, O >= 1.  Returns 0, 1 (bad arguments), 2 (HIP error): mgn_loss_last_error(). */
 #define MGN_LOSS_MAX_TERMS 8
 #define MGN_LOSS_MAX_F 4
@@ -733,6 +736,7 @@ typedef struct {
   float* a_out; float* bu_out; float* b_out; /* [N, F, DX], [N, F], [N, O]: per-node derivatives kept for the backward */
   float* part;                               /* mgn_loss_workspace_bytes() of scratch */
   float* terms; float* total; float* invcount;   /* [nterms] weighted terms, their sum, 1 / selected rows (device scalars) */
+  const uint8_t* exclude;                    /* optional [N]: != 0 leaves the row out of every mean */
 } mgn_loss_args;
 /* neighbour CSR rows without self entries; self_loop (optional, [N]) != 0 where the edge list holds a pair (n, n) */
 int mgn_loss_fd_geometry(const int64_t* rowptr, const int32_t* col, const uint8_t* self_loop, const float* pos, int DX, int64_t N,
@@ -798,7 +802,9 @@ const char* mgn_khop_last_error(void);
  *
  * mgn_gather_rows_batch: dst[r, :width] = src[idx[r], :width], r < rows, for up to MGN_MAX_GATHER_JOBS jobs in ONE launch;
  * rows of 32-bit elements, any width >= 1, any leading dimensions >= width (in elements), 64-bit row counts and indices.  An
- * index outside [0, src_rows) is not followed (that row of dst is left as it is).  Never synchronises: capturable. */
+ * index outside [0, src_rows) is not followed (that row of dst is left as it is), so two jobs with one dst and complementary
+ * indices merge two sources row by row in the same launch: the latent rows and the [MASK] rows of a reconstructed mesh
+ * (meshmask.reconstruct_graph).  Never synchronises: capturable. */
 #define MGN_MAX_GATHER_JOBS 8
 typedef struct {
   const float* src;    /* [src_rows, ld_src] */

@@ -226,6 +226,10 @@ extern "C" int mgn_morton_order(const float* pos, int ld, int D, int64_t N, int3
 // every thread owns one node i and tests it against the tile when it is an OBSTACLE.  Matches are
 // appended through one atomic counter (order irrelevant: the keys are sorted afterwards).
 #define WE_TILE 256
+// the reference compares the FLOAT type column with the codes (preprocessing.py:122-130): 1.5 is no OBSTACLE, 0.5 no NORMAL
+__device__ __forceinline__ int world_class(float t) {
+  return t == (float)MGN_NODE_OBSTACLE ? MGN_NODE_OBSTACLE : t == (float)MGN_NODE_NORMAL ? MGN_NODE_NORMAL : -1;
+}
 template <int D>
 __global__ void __launch_bounds__(WE_TILE) k_world_pairs(const float* __restrict__ x, int x_w, int pos0, int type_idx, long N, double r2,
                                                         uint64_t* __restrict__ keys, unsigned long long* __restrict__ count, unsigned long long cap) {
@@ -235,14 +239,14 @@ __global__ void __launch_bounds__(WE_TILE) k_world_pairs(const float* __restrict
   double pi[D];
   int ti = -1;
   if (i < N) {
-    ti = (int)(long)x[i * x_w + type_idx];
+    ti = world_class(x[i * x_w + type_idx]);
 #pragma unroll
     for (int d = 0; d < D; ++d) pi[d] = (double)x[i * x_w + pos0 + d];
   }
   for (long j0 = 0; j0 < N; j0 += WE_TILE) {
     const long j = j0 + threadIdx.x;
     __syncthreads();
-    tt[threadIdx.x] = (j < N) ? (int)(long)x[j * x_w + type_idx] : -1;
+    tt[threadIdx.x] = (j < N) ? world_class(x[j * x_w + type_idx]) : -1;
 #pragma unroll
     for (int d = 0; d < D; ++d) tp[threadIdx.x][d] = (j < N) ? (double)x[j * x_w + pos0 + d] : 0.0;
     __syncthreads();
@@ -503,8 +507,8 @@ __global__ void __launch_bounds__(256) k_sim_post(const float* __restrict__ x, i
   const float sd = fmaxf(sqrtf(fmaxf(var, 0.f)), std_eps);
   float p = x[row * x_w + out_start + col] + (net_out[i] * sd + mean);
   if (mask_truth) {
-    const int t = (int)(long)x[row * x_w + type_idx];
-    if (!(t == MGN_NODE_NORMAL || t == MGN_NODE_OUTFLOW)) p = y[row * y_w + col];
+    const float t = x[row * x_w + type_idx];  // the FLOAT is compared (lightning_module.py:27-35): 0.5 is not NORMAL
+    if (!(t == (float)MGN_NODE_NORMAL || t == (float)MGN_NODE_OUTFLOW)) p = y[row * y_w + col];
   }
   pred[i] = p;
 }

@@ -151,7 +151,7 @@ class Simulator(nn.Module):
             if mask_truth:
                 t = inputs.x[:, self.node_type_index]
                 keep = torch.logical_or(t == int(NodeType.NORMAL), t == int(NodeType.OUTFLOW))
-                pred = torch.where(keep.unsqueeze(1), pred, inputs.y)
+                pred = torch.where(keep.unsqueeze(1), pred, inputs.y[:, :self.output_size])
             return pred
         x = inputs.x.contiguous()
         y = inputs.y.contiguous() if (mask_truth and inputs.y is not None) else None
@@ -168,11 +168,13 @@ class Simulator(nn.Module):
         return inputs.x[:, self.output_index_start: self.output_index_end]
 
     def _get_target_normalized(self, inputs, is_training: bool = True) -> torch.Tensor:
-        return self._output_normalizer(inputs.y - self._get_pre_target(inputs), is_training)
+        # the first output_size columns of y, like the fused kernels (a y exactly that wide is the reference's statement)
+        return self._output_normalizer(inputs.y[:, :self.output_size] - self._get_pre_target(inputs), is_training)
 
     def _get_one_hot_type(self, inputs) -> torch.Tensor:
         node_type = inputs.x[:, self.node_type_index]
-        return torch.nn.functional.one_hot(torch.squeeze(node_type.long()), NodeType.SIZE)
+        # (the reference squeezes the column: the same for N > 1; one row would lose its dimension, and the fused kernels take N = 1)
+        return torch.nn.functional.one_hot(node_type.long().reshape(-1), NodeType.SIZE)
 
     def _build_node_features(self, inputs, one_hot_type: torch.Tensor) -> torch.Tensor:
         features = inputs.x[:, self.feature_index_start: self.feature_index_end]

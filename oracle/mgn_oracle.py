@@ -480,8 +480,8 @@ def add_world_edges_oracle(x, edge_index, world_pos_index_start: int, world_pos_
     xn = np.asarray(x, dtype=np.float32)
     N = xn.shape[0]
     wp = xn[:, world_pos_index_start:world_pos_index_end].astype(np.float64)
-    t = xn[:, node_type_index].astype(np.int64)
-    obs, nor = np.nonzero(t == 1)[0], np.nonzero(t == 0)[0]
+    t = xn[:, node_type_index]  # the FLOAT is compared with the codes (:122-130): 1.5 is no OBSTACLE, 0.5 no NORMAL
+    obs, nor = np.nonzero(t == 1.0)[0], np.nonzero(t == 0.0)[0]
     d2 = ((wp[obs][:, None, :] - wp[nor][None, :, :]) ** 2).sum(-1)
     io, jn = np.nonzero(d2 <= float(radius) ** 2)
     a, b = obs[io], nor[jn]

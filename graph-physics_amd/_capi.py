@@ -18,8 +18,10 @@ SOURCES = [os.path.join(_CSRC, "mgn_kernels.hip"), os.path.join(_CSRC, "mgn_prep
            os.path.join(_CSRC, "mgn_dense.hip"), os.path.join(_CSRC, "mgn_loss.hip"), os.path.join(_CSRC, "mgn_khop.hip"),
            os.path.join(_CSRC, "mgn_subgraph.hip"), os.path.join(_CSRC, "mgn_randedge.hip"), os.path.join(_CSRC, "mgn_knn.hip")]
 DEPS = [os.path.join(_CSRC, "mgn_x6.inc"), os.path.join(_CSRC, "mgn_fused.inc"), os.path.join(_CSRC, "mgn_pp.inc"), os.path.join(_CSRC, "mgn_ppr.inc"),
-        os.path.join(_CSRC, "mgn_philox.inc"), os.path.join(_CSRC, "mgn_host.inc"), os.path.join(_CSRC, "mgn_graphprim.inc")]  # included by the sources
+        os.path.join(_CSRC, "mgn_philox.inc"), os.path.join(_CSRC, "mgn_host.inc"), os.path.join(_CSRC, "mgn_graphprim.inc"),
+        os.path.join(_CSRC, "mgn_rollout.inc")]  # included by the sources
 HEADER = os.path.join(_REPO, "include", "mgn_hip.h")
+EXT_HEADER = os.path.join(_REPO, "include", "mgn_hip_ext.h")  # entry points added after ABI 136 (EXT_SYMBOLS)
 # No packed-fp32 VALU (v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32) in device code: beside a SIMD partner that streams MFMAs
 # one of them takes ~70 cycles instead of ~6 (tools/coissue_probe.hip; plain VALU: 8), and hipcc forms them everywhere --
 # the SLP vectorizer out of scalar code, the legalizer out of float4 arithmetic (csrc/Makefile carries the same flags).
@@ -330,7 +332,16 @@ UNITS = {"kernels": {
     "mgn_knn_last_error": (C.c_char_p, []),
 }}
 SYMBOLS = {name: sig for group in UNITS.values() for name, sig in group.items()}
+#: every symbol include/mgn_hip_ext.h declares (entry points added after ABI 136: scalar and pointer arguments only), name ->
+#: (restype, argtypes); all of them are defined under csrc/mgn_prep.hip and report through mgn_prep_last_error
+EXT_SYMBOLS = {
+    "mgn_rollout_tail_scratch_floats": (C.c_int, []),
+    "mgn_rollout_tail": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_float, C.POINTER(C.c_float), C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+}
 _UNIT_OF = {name: unit for unit, group in UNITS.items() for name in group}
+_UNIT_OF.update({name: "prep" for name in EXT_SYMBOLS})
 
 _lib = None
 _lock = threading.Lock()
@@ -357,7 +368,7 @@ def source_hash() -> str:
     import hashlib
 
     h = hashlib.sha256()
-    for f in SOURCES + DEPS + [HEADER]:
+    for f in SOURCES + DEPS + [HEADER, EXT_HEADER]:
         with open(f, "rb") as fh:
             h.update(os.path.basename(f).encode() + b"\0" + fh.read() + b"\0")
     h.update(" ".join(DEVICE_FLAGS).encode())  # a library built with other code-generation flags is stale too
@@ -430,7 +441,7 @@ def lib():
                 L = C.CDLL(LIB_PATH)
             except OSError as e:
                 raise RuntimeError(f"cannot load {LIB_PATH}: {e}") from e
-            for name, (res, args) in SYMBOLS.items():
+            for name, (res, args) in list(SYMBOLS.items()) + list(EXT_SYMBOLS.items()):
                 fn = getattr(L, name)
                 fn.restype = res
                 fn.argtypes = args

@@ -492,13 +492,12 @@ extern "C" int mgn_sim_pre(const mgn_sim_desc* desc, void* ws, size_t ws_bytes, 
 // build_outputs + the rollout's ground-truth re-imposition (simulator.py:186-191,
 // lightning_module.py:27-35,375-409):  pred = x[:, os:oe] + net_out * std + mean, and where the
 // node type is not NORMAL / OUTFLOW the ground truth y is written instead (mask_truth != 0).
-__global__ void __launch_bounds__(256) k_sim_post(const float* __restrict__ x, int x_w, int out_start, int type_idx,
-                                                  const float* __restrict__ y, int y_w, const float* __restrict__ net_out, int O,
-                                                  const float* __restrict__ acc_sum, const float* __restrict__ acc_sumsq,
-                                                  const float* __restrict__ acc_count, float std_eps, int mask_truth,
-                                                  long N, float* __restrict__ pred) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= N * O) return;
+// element i = row * O + col of the prediction: the one statement of this arithmetic (k_sim_post, and k_rollout_tail of
+// mgn_rollout.inc, whose predictions are bit-identical to mgn_sim_post's by construction)
+__device__ __forceinline__ float sim_post_value(const float* __restrict__ x, int x_w, int out_start, int type_idx,
+                                                const float* __restrict__ y, int y_w, const float* __restrict__ net_out, int O,
+                                                const float* __restrict__ acc_sum, const float* __restrict__ acc_sumsq,
+                                                const float* __restrict__ acc_count, float std_eps, int mask_truth, long i) {
   const long row = i / O;
   const int col = (int)(i % O);
   const float cnt = fmaxf(*acc_count, 1.0f);
@@ -510,7 +509,17 @@ __global__ void __launch_bounds__(256) k_sim_post(const float* __restrict__ x, i
     const float t = x[row * x_w + type_idx];  // the FLOAT is compared (lightning_module.py:27-35): 0.5 is not NORMAL
     if (!(t == (float)MGN_NODE_NORMAL || t == (float)MGN_NODE_OUTFLOW)) p = y[row * y_w + col];
   }
-  pred[i] = p;
+  return p;
+}
+
+__global__ void __launch_bounds__(256) k_sim_post(const float* __restrict__ x, int x_w, int out_start, int type_idx,
+                                                  const float* __restrict__ y, int y_w, const float* __restrict__ net_out, int O,
+                                                  const float* __restrict__ acc_sum, const float* __restrict__ acc_sumsq,
+                                                  const float* __restrict__ acc_count, float std_eps, int mask_truth,
+                                                  long N, float* __restrict__ pred) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= N * O) return;
+  pred[i] = sim_post_value(x, x_w, out_start, type_idx, y, y_w, net_out, O, acc_sum, acc_sumsq, acc_count, std_eps, mask_truth, i);
 }
 
 extern "C" int mgn_sim_post(const float* x, int x_w, int out_start, int type_idx, const float* y, int y_w, const float* net_out,
@@ -748,6 +757,8 @@ extern "C" int mgn_masked_mse_bwd(const float* out, int ldo, const float* tgt, i
                      (long)N, O, t[0], t[1], t[2], t[3], inv, g, d_out);
   return check_launch("mgn_masked_mse_bwd");
 }
+
+#include "mgn_rollout.inc"  // the validation rollout's fused tail: sim_post_value + the feedback delta + the frame's metrics
 
 // ---- the same tail in TWO launches whatever the number of tensors (376 for the 15-round model: four launches of each kernel above,
 // each under-filling the GPU -- 130 us of a 3.3 ms one-mesh step).  What is fixed across steps (parameter / moment pointers, lengths,

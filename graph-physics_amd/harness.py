@@ -8,7 +8,10 @@ GPU box):
     AdamW(lr, betas=(0.9,0.95), weight_decay=1e-4) + cosine warm-up
     (lightning_module.py:494-511, utils/scheduler.py:51-67);
   * rollout  (lightning_module.py:375-409): autoregressive feedback of the last
-    prediction, ground truth re-imposed on the non NORMAL/OUTFLOW nodes.
+    prediction (with ``use_previous_data`` also of ``prediction - current output``),
+    ground truth re-imposed on the non NORMAL/OUTFLOW nodes;
+  * validation  (lightning_module.py:411-492): ``Engine.validate``, the rollout plus
+    ``val_loss`` / ``val_all_rollout_rmse`` / ``val_1step_rmse`` from sums kept on the device.
 
 These are what ``bench.py`` times ("training steps/sec", "rollout nodes*steps/sec").
 """
@@ -177,7 +180,11 @@ class Engine:
     """Model + simulator + optimiser for one device."""
 
     def __init__(self, param: Dict[str, Any], device: torch.device, learning_rate: float = 1e-4,
-                 num_steps: int = 1000, warmup: int = 100, grad_clip: float = 1.0):
+                 num_steps: int = 1000, warmup: int = 100, grad_clip: float = 1.0, loss_masks: Optional[Sequence[int]] = None,
+                 use_previous_data: bool = False, previous_data_start: Optional[int] = None,
+                 previous_data_end: Optional[int] = None):
+        """``loss_masks`` (the LightningModule's ``masks``), ``use_previous_data``, ``previous_data_start`` and
+        ``previous_data_end`` are the LightningModule's arguments of the same names (lightning_module.py:48-51)."""
         self.param, self.device = param, device
         _ops.set_matrix_precision(matrix_precision_from_config(param))  # bf16-mixed <=> enable_vram_optimizations
         self.model = get_model(param)
@@ -185,7 +192,16 @@ class Engine:
         # the config's "loss" section (lightning_module.py:86-96); without one: the masked L2, on the code path it always took
         self.loss, self.loss_name = get_loss(param)
         self.gradient_method = get_gradient_method(param)
-        self.loss_masks = (NodeType.NORMAL, NodeType.OUTFLOW)
+        self.loss_masks = tuple(loss_masks) if loss_masks is not None else (NodeType.NORMAL, NodeType.OUTFLOW)
+        #: autoregressive feedback of ``prediction - current output`` into x[:, previous_data_start:previous_data_end]
+        #: (lightning_module.py:383-386,400-401)
+        self.use_previous_data = bool(use_previous_data)
+        self.previous_data_start, self.previous_data_end = previous_data_start, previous_data_end
+        if self.use_previous_data:
+            self._check_previous_data()
+        self._tail_part = None   # scratch of mgn_rollout_tail
+        self._v_table = None     # (metrics [cap, 4] fp64, slot int32 [1], cap) of validate()
+        self._f_steps = {}       # captured frame steps with the fused tail: "rollout" (previous data), "validate"
         #: per-term device scalars of the last step of a MultiLoss config, in the order of ``loss_name`` (what the reference logs as
         #: ``train_<name>``: the WEIGHTED terms); None for a single loss
         self.last_losses = None
@@ -217,7 +233,7 @@ class Engine:
     def _loss(self, batch: Graph, net_out: torch.Tensor, target: torch.Tensor, node_type: torch.Tensor) -> torch.Tensor:
         """the training step's loss (lightning_module.py:278-312)"""
         if isinstance(self.loss, L2Loss):
-            return l2_loss(net_out, target, node_type)
+            return l2_loss(net_out, target, node_type, self.loss_masks)
         if not isinstance(self.loss, MultiLoss):
             return self.loss(graph=batch, target=target, network_output=net_out, node_type=node_type, masks=self.loss_masks,
                              gradient_method=self.gradient_method)
@@ -394,6 +410,26 @@ class Engine:
         self._r_seen = {}
         return g
 
+    @staticmethod
+    def _put_frame(st: Graph, fr: Graph, seen: dict):
+        """copy a frame's fields into the static tensors ``st`` of a captured step; ``seen``: name -> (tensor, version) copied last"""
+        def put(name, dst, src, may_skip):
+            # (the skip is for the MESH's fields only -- edge features, positions: tensors nobody refills in place; x / y are copied
+            # every frame: the engine's own kernels write through raw pointers without bumping _version)
+            last = seen.get(name)
+            if src is dst or (may_skip and last is not None and last[0] is src and last[1] == src._version):
+                return
+            dst.copy_(src, non_blocking=True)
+            seen[name] = (src, src._version)
+
+        if fr is not st:
+            put("x", st.x, fr.x, False)
+            put("y", st.y, fr.y, False)
+            put("edge_attr", st.edge_attr, fr.edge_attr, True)
+            # a deforming mesh: positions are per frame (relative RoPE reads them inside the captured step)
+            if st.pos is not None and getattr(fr, "pos", None) is not None:
+                put("pos", st.pos, fr.pos, True)
+
     @torch.no_grad()
     def rollout_graphed(self, frames: Sequence[Graph]) -> List[torch.Tensor]:
         """``rollout`` through the captured step (same shapes / topology for every frame)."""
@@ -405,24 +441,8 @@ class Engine:
         seen = getattr(self, "_r_seen", None)
         if seen is None:
             seen = self._r_seen = {}
-
-        def put(name, dst, src, may_skip):
-            # (the skip is for the MESH's fields only -- edge features, positions: tensors nobody refills in place; x / y are copied
-            # every frame: the engine's own kernels write through raw pointers without bumping _version)
-            last = seen.get(name)
-            if src is dst or (may_skip and last is not None and last[0] is src and last[1] == src._version):
-                return
-            dst.copy_(src, non_blocking=True)
-            seen[name] = (src, src._version)
-
         for k, fr in enumerate(frames):
-            if fr is not st:
-                put("x", st.x, fr.x, False)
-                put("y", st.y, fr.y, False)
-                put("edge_attr", st.edge_attr, fr.edge_attr, True)
-                # a deforming mesh: positions are per frame (relative RoPE reads them inside the captured step)
-                if st.pos is not None and getattr(fr, "pos", None) is not None:
-                    put("pos", st.pos, fr.pos, True)
+            self._put_frame(st, fr, seen)
             if k == 0:
                 self._r_last.copy_(fr.x[:, i0:i1])
             self._r_graph.replay()
@@ -461,6 +481,27 @@ class Engine:
         "on" -- one step captured in a hipGraph and replayed (the frames must share one mesh and one shape); "auto" (default) --
         replay when they do, the trajectory is long enough to pay for the capture and the mesh is small enough to be
         launch-bound; same results either way (tests/test_hip_parity.py: graphed == eager)."""
+        key = self._replay_key(frames, graph)
+        if self.use_previous_data:
+            return self._rollout_previous_data(frames, key)
+        if key is not None:
+            # the keyed edge_index is kept REFERENCED and compared by identity: an address alone may be recycled by the allocator
+            # for another trajectory's topology of the same size
+            if (getattr(self, "_r_key", None) != key or getattr(self, "_r_graph", None) is None
+                    or getattr(self, "_r_ei", None) is not frames[0].edge_index):
+                self.capture_rollout_step(frames[0])
+                self._r_key = key
+                self._r_ei = frames[0].edge_index
+            return self.rollout_graphed(frames)
+        last, out = None, []
+        for fr in frames:
+            last = self.predict_step(fr, last)
+            out.append(last)
+        return out
+
+    def _replay_key(self, frames: Sequence[Graph], graph: str):
+        """the capture key of ``frames`` (``_rollout_graph_key``) when ``rollout`` / ``validate`` are to replay a captured step
+        under the mode ``graph``, None when every step is driven from Python"""
         if graph not in ("auto", "on", "off"):
             raise ValueError("graph must be 'auto', 'on' or 'off'")
         import torch.distributed as _dist
@@ -472,16 +513,228 @@ class Engine:
             if graph == "on" and key is None:
                 raise ValueError("rollout(graph='on') needs frames of one shape on one edge_index tensor")
             if key is not None and (graph == "on" or small):
-                # the keyed edge_index is kept REFERENCED and compared by identity: an address alone may be recycled by the allocator
-                # for another trajectory's topology of the same size
-                if (getattr(self, "_r_key", None) != key or getattr(self, "_r_graph", None) is None
-                        or getattr(self, "_r_ei", None) is not frames[0].edge_index):
-                    self.capture_rollout_step(frames[0])
-                    self._r_key = key
-                    self._r_ei = frames[0].edge_index
-                return self.rollout_graphed(frames)
-        last, out = None, []
-        for fr in frames:
-            last = self.predict_step(fr, last)
-            out.append(last)
+                return key
+        return None
+
+    # ------------------------------------------------- previous data and validation (lightning_module.py:375-492)
+    def _check_previous_data(self):
+        s, p0, p1 = self.sim, self.previous_data_start, self.previous_data_end
+        if p0 is None or p1 is None:
+            raise ValueError("use_previous_data needs previous_data_start and previous_data_end")
+        p0, p1 = int(p0), int(p1)
+        if p0 < 0 or p1 <= p0:
+            raise ValueError(f"previous-data columns [{p0}, {p1}) are no column range of x")
+        if p1 - p0 != s.output_size:
+            raise ValueError(f"previous-data columns [{p0}, {p1}) hold {p1 - p0} columns, the simulator's output has {s.output_size}")
+        if p0 < s.output_index_end and s.output_index_start < p1:
+            raise ValueError(f"previous-data columns [{p0}, {p1}) overlap the output columns "
+                             f"[{s.output_index_start}, {s.output_index_end})")
+        if p0 <= s.node_type_index < p1:
+            raise ValueError(f"previous-data columns [{p0}, {p1}) contain the node-type column {s.node_type_index}")
+        self.previous_data_start, self.previous_data_end = p0, p1
+
+    def _tail(self, b: Graph, net_out: torch.Tensor, table):
+        """What follows the model in a rollout frame (lightning_module.py:387-401,439-455): ``(pred, prev)`` with ``pred`` =
+        build_outputs with the ground truth re-imposed and ``prev = pred - x[:, output columns]`` (None unless
+        ``use_previous_data``); with ``table = (metrics [cap, 4] fp64, slot int32 [1], cap)`` the frame's row {S_all, S_loss,
+        n_loss, N} goes to ``metrics[slot]`` and ``slot`` advances, without a host synchronisation.  One engine call
+        (``mgn_rollout_tail``) on the device; the same formulas as torch statements for CPU tensors and outputs wider than 32."""
+        sim = self.sim
+        O, i0 = sim.output_size, sim.output_index_start
+        y = getattr(b, "y", None)
+        if y is None:
+            raise ValueError("a rollout frame needs y: the ground truth is re-imposed on the boundary nodes")
+        N = int(b.x.shape[0])
+        if sim._can_fuse(b) and net_out.is_cuda and (table is None or 1 <= len(self.loss_masks) <= 4):
+            import ctypes as C
+            from . import _capi
+            dev = b.x.device
+            x, y = b.x.contiguous(), y.contiguous()
+            sim._check_widths(x, y, None)
+            no = net_out.detach().to(torch.float32).contiguous()
+            pred = torch.empty(N, O, dtype=torch.float32, device=dev)
+            prev = torch.empty(N, O, dtype=torch.float32, device=dev) if self.use_previous_data else None
+            if self._tail_part is None or self._tail_part.device != dev:
+                self._tail_part = torch.empty(_capi.lib().mgn_rollout_tail_scratch_floats(), dtype=torch.float32, device=dev)
+            types = (C.c_float * len(self.loss_masks))(*[float(int(t)) for t in self.loss_masks])
+            m, slot, cap = table if table is not None else (None, None, 0)
+            nz = sim._output_normalizer
+            call("mgn_rollout_tail", dev, x.data_ptr(), x.shape[1], i0, sim.node_type_index, y.data_ptr(), y.shape[1], no.data_ptr(), O,
+                 nz._acc_sum.data_ptr(), nz._acc_sum_squared.data_ptr(), nz._acc_count.data_ptr(), float(nz._std_epsilon_value),
+                 types, len(types), N, pred.data_ptr(), (prev.data_ptr() if prev is not None else None), self._tail_part.data_ptr(),
+                 (m.data_ptr() if m is not None else None), (slot.data_ptr() if slot is not None else None), cap)
+            return pred, prev
+        pred = sim.predict(b, net_out, mask_truth=True)
+        prev = pred - b.x[:, i0:i0 + O] if self.use_previous_data else None
+        if table is not None:
+            m, slot, cap = table
+            t = b.x[:, sim.node_type_index]
+            w = torch.zeros_like(t, dtype=torch.bool)
+            for code in self.loss_masks:
+                w = torch.logical_or(w, t == int(code))
+            d2 = (pred - y[:, :O]).double() ** 2
+            row = torch.stack([d2.sum(), (d2 * w.unsqueeze(1)).sum(), w.double().sum(),
+                               torch.full((), float(N), dtype=torch.float64, device=pred.device)])
+            at = slot.long().clamp(max=cap - 1)   # a device index: no synchronisation; a full table keeps its last row
+            m.index_copy_(0, at, torch.where(slot < cap, row, m.index_select(0, at)[0]).unsqueeze(0))
+            slot += 1
+        return pred, prev
+
+    def _frame(self, batch: Graph, last_prediction, last_previous_data, table):
+        self.sim.eval()
+        batch = batch.clone()
+        i0, i1 = self.sim.output_index_start, self.sim.output_index_end
+        if self.use_previous_data and self.previous_data_end > batch.x.shape[1]:
+            raise ValueError(f"previous-data columns [{self.previous_data_start}, {self.previous_data_end}) are outside x "
+                             f"(width {batch.x.shape[1]})")
+        if last_prediction is not None:
+            batch.x[:, i0:i1] = last_prediction
+            if self.use_previous_data:
+                batch.x[:, self.previous_data_start:self.previous_data_end] = last_previous_data
+        graph, _ = self.sim._build_input_graph(batch, False)
+        pred, prev = self._tail(batch, self.sim.model(graph), table)
+        return batch, pred, batch.y, pred, (prev if self.use_previous_data else last_previous_data)
+
+    @torch.no_grad()
+    def make_prediction(self, batch: Graph, last_prediction: Optional[torch.Tensor], last_previous_data: Optional[torch.Tensor]):
+        """``LightningModule._make_prediction`` (lightning_module.py:375-409): the frame with the last prediction -- and, with
+        ``use_previous_data``, the last ``prediction - current output`` -- fed back, one Simulator forward in eval mode, the
+        ground truth re-imposed on the nodes that are not NORMAL / OUTFLOW.  Returns the reference's 5-tuple
+        ``(batch, predicted_outputs, target, last_prediction, last_previous_data)``."""
+        return self._frame(batch, last_prediction, last_previous_data, None)
+
+    @torch.no_grad()
+    def _frame_step(self, mode: str, key, frame: Graph, table, warmup: int = 2):
+        """The captured form of ``_frame`` for trajectories of one mesh and shape (``capture_rollout_step`` with the fused
+        tail): kept per ``mode`` until ``key`` or the edge_index object changes."""
+        S = self._f_steps.get(mode)
+        if S is not None and S["key"] == key and S["ei"] is frame.edge_index:
+            return S
+        dev = self.device
+        self.sim.eval()
+        st = frame.clone()
+        if getattr(frame, "mgn_topology", None) is not None:
+            st.mgn_topology = frame.mgn_topology
+        else:
+            st.mgn_topology = _ops.Topology(st.edge_index, st.x.shape[0])
+        i0, i1 = self.sim.output_index_start, self.sim.output_index_end
+        p0, p1 = self.previous_data_start, self.previous_data_end
+        last = st.x[:, i0:i1].clone()
+        plast = st.x[:, p0:p1].clone() if self.use_previous_data else None
+
+        def body():
+            b = Graph(x=st.x.clone(), y=st.y, pos=st.pos, edge_attr=st.edge_attr, edge_index=st.edge_index)
+            b.mgn_topology = st.mgn_topology
+            b.x[:, i0:i1] = last
+            if plast is not None:
+                b.x[:, p0:p1] = plast
+            graph, _ = self.sim._build_input_graph(b, False)
+            pred, prev = self._tail(b, self.sim.model(graph), table)
+            last.copy_(pred)
+            if plast is not None:
+                plast.copy_(prev)
+            return pred
+
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(stream_object(dev))
+        with torch.cuda.stream(side):
+            for _ in range(max(1, warmup)):   # (these advance the metrics slot: validate() sets it after the capture)
+                body()
+        stream_object(dev).wait_stream(side)
+        torch.cuda.synchronize(dev)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            pred = body()
+        S = self._f_steps[mode] = dict(key=key, ei=frame.edge_index, graph=g, st=st, last=last, plast=plast, pred=pred)
+        return S
+
+    @torch.no_grad()
+    def _frames_graphed(self, S, frames: Sequence[Graph]) -> List[torch.Tensor]:
+        """one trajectory through the captured step ``S``: the feedback state restarts from the first frame's own columns"""
+        i0, i1 = self.sim.output_index_start, self.sim.output_index_end
+        out, seen = [], {}
+        for k, fr in enumerate(frames):
+            self._put_frame(S["st"], fr, seen)
+            if k == 0:
+                S["last"].copy_(fr.x[:, i0:i1])
+                if S["plast"] is not None:
+                    S["plast"].copy_(fr.x[:, self.previous_data_start:self.previous_data_end])
+            S["graph"].replay()
+            out.append(S["pred"].clone())
         return out
+
+    def _previous_data_key(self):
+        return (self.use_previous_data, self.previous_data_start, self.previous_data_end)
+
+    def _rollout_previous_data(self, frames: Sequence[Graph], key) -> List[torch.Tensor]:
+        if key is not None:
+            return self._frames_graphed(self._frame_step("rollout", key + self._previous_data_key(), frames[0], None), frames)
+        last = prev = None
+        out = []
+        for fr in frames:
+            _, pred, _, last, prev = self._frame(fr, last, prev, None)
+            out.append(pred)
+        return out
+
+    def _metrics_table(self, rows: int, dev: torch.device):
+        """the device table validate() fills: kept between calls (its address is part of a captured step), regrown in powers of two"""
+        t = self._v_table
+        if t is None or t[2] < rows or t[0].device != dev:
+            cap = max(1024, 1 << (rows - 1).bit_length())
+            t = self._v_table = (torch.zeros(cap, 4, dtype=torch.float64, device=dev), torch.zeros(1, dtype=torch.int32, device=dev), cap)
+        return t
+
+    @torch.no_grad()
+    def validate(self, trajectories: Sequence[Sequence[Graph]], graph: str = "auto") -> Dict[str, Any]:
+        """The validation loop (``validation_step`` / ``on_validation_epoch_end``, lightning_module.py:411-492) over
+        ``trajectories``, a sequence of frame sequences; the feedback state restarts with every trajectory
+        (``_reset_validation_trajectory``).  Returns
+
+          * ``val_loss``: the mean over all frames of the masked L2 of the frame, ``S_loss / (n_loss * O)`` over the rows whose
+            type is in ``loss_masks``.  (Lightning's epoch mean weights a step by its batch size; the reference validates one
+            graph per batch, so that is the plain mean over the frames.)
+          * ``val_all_rollout_rmse = sqrt(sum S_all / (sum N * O))``: the reference's concatenate-then-mean;
+          * ``val_1step_rmse``: the mean over the trajectories of ``sqrt(S_all / (N * O))`` of their first frame;
+          * ``val_loss_per_step``: the per-frame losses, a CPU double tensor in frame order;
+          * ``predictions``: per trajectory the list of predicted outputs (device tensors).
+
+        ``S_all`` is the frame's sum of ``(prediction - y)^2``, ``S_loss`` the same over the loss rows.  On the device every frame
+        is one Simulator forward plus one engine call that leaves its four numbers in a device table (``mgn_rollout_tail``): no
+        host synchronisation and no device-to-host copy inside the frame loop, table and row counter are read once after the
+        last frame.  ``graph`` as in :meth:`rollout`; the eager and the captured step give the same bits."""
+        total = sum(len(tr) for tr in trajectories)
+        if total == 0:
+            raise ValueError("validate needs at least one frame")
+        dev = next(tr[0].x.device for tr in trajectories if len(tr) > 0)
+        table = self._metrics_table(total, dev)
+        m, slot, cap = table
+        slot.zero_()
+        preds, first, base = [], [], 0
+        for frames in trajectories:
+            key = self._replay_key(frames, graph)
+            if key is not None:
+                S = self._frame_step("validate", key + self._previous_data_key() + (m.data_ptr(), cap, self.loss_masks), frames[0], table)
+            slot.fill_(base)   # this trajectory's first row, whatever a capture's warm-up steps did
+            if key is not None:
+                out = self._frames_graphed(S, frames)
+            else:
+                last = prev = None
+                out = []
+                for fr in frames:
+                    _, pred, _, last, prev = self._frame(fr, last, prev, table)
+                    out.append(pred)
+            if len(frames) > 0:
+                first.append(base)
+            base += len(frames)
+            preds.append(out)
+        host = torch.cat([m[:total].reshape(-1), slot.to(torch.float64)]).cpu()   # the one device-to-host copy
+        if int(host[-1]) > cap or int(host[-1]) != total:
+            raise RuntimeError(f"validate: the metrics table holds {cap} rows and its counter reads {int(host[-1])} after "
+                               f"{total} frames")
+        S_all, S_loss, n_loss, rows = host[:-1].reshape(total, 4).unbind(1)
+        O = self.sim.output_size
+        per_step = S_loss / (n_loss * O)
+        return {"val_loss": float(per_step.mean()),
+                "val_all_rollout_rmse": float(torch.sqrt(S_all.sum() / (rows.sum() * O))),
+                "val_1step_rmse": float(torch.sqrt(S_all[first] / (rows[first] * O)).mean()),
+                "val_loss_per_step": per_step, "predictions": preds}

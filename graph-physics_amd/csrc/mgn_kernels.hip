@@ -2105,395 +2105,6 @@ __global__ void __launch_bounds__(256) k_csr_sortbig(const int32_t* __restrict__
 // ============================================================================ C ABI
 #include "mgn_host.inc"  // g_err, fail, check_launch
 
-struct MlpPlan {
-  bool lds;       // LDS-weight kernel (H = 128, full widths)
-  int mt;         // 16-row tiles per wave
-  unsigned grid;  // workgroups
-  size_t smem;    // dynamic LDS bytes
-};
-
-static bool fwd_ragged(const mgn_mlp_fwd_args& a) {
-  bool r = (a.out_w != a.H);
-  for (int p = 0; p < a.nphase; ++p) r = r || (a.kw[p] != a.H);
-  return r;
-}
-
-static MlpPlan plan_mlp(int64_t M, int H, int NL, bool ragged, bool bwd, int act = MGN_ACT_RELU) {
-  MlpPlan p;
-  p.lds = (H == 128) && !ragged && NL >= (bwd ? 2 : 1) && NL <= LDS_MAX_NL;
-  if (getenv("MGN_NO_LDS") != nullptr) p.lds = false;
-  if (act == MGN_ACT_GELU) p.lds = false;  // GELU lives on the generic kernels only (a stand-alone build_mlp option)
-  p.mt = (M >= (int64_t)64 * 2048) ? 2 : 1;
-  // measured on MI355X (tools/kbench.py, E = 180k): with LDS-shared weights the forward is
-  // faster at 16 rows per wave (172 VGPRs, no spills: 352 vs 368 us), the backward chain at 32
-  if (p.lds) p.mt = 1;
-  if (const char* e = getenv("MGN_MT")) p.mt = (atoi(e) == 2) ? 2 : 1;
-  const int rows = 64 * p.mt;
-  p.grid = (unsigned)((M + rows - 1) / rows);
-  if (p.lds && p.grid > 512) p.grid = 512;  // persistent: 2 workgroups per CU walk the tiles
-  if (const char* e = getenv("MGN_GRID")) { if (p.lds && !bwd && atoi(e) > 0 && (unsigned)atoi(e) < p.grid) p.grid = (unsigned)atoi(e); }
-  p.smem = p.lds ? (bwd ? (size_t)2 * WBUF_BYTES + 512 + (size_t)4 * (NL + 1) * H * sizeof(float) : (size_t)FWD_LDS_BYTES) : 0;
-  return p;
-}
-
-template <typename K>
-static int set_smem(K kern) {
-  static thread_local const void* done[16];
-  static thread_local int ndone = 0;
-  for (int i = 0; i < ndone; ++i)
-    if (done[i] == (const void*)kern) return 0;
-  if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * WBUF_BYTES + 4 * 7 * 128 * 4)) != hipSuccess) return 1;
-  if (ndone < 16) done[ndone++] = (const void*)kern;
-  return 0;
-}
-
-// split-bf16 kernels: every GEMM unit of the launch comes packed (and the fp32 override is off)
-static bool fwd_x6(const mgn_mlp_fwd_args& a) {
-  if (a.wpk[0] == nullptr || getenv("MGN_FP32_MFMA") != nullptr) return false;
-  const int G = a.nphase + a.NL - 1 + a.n_post;
-  if (G > X6_MAX_UNITS || a.NL > LDS_MAX_NL) return false;
-  // register sharing inside the kernel: gathered adds ride in the next-phase buffer
-  if (a.n_add > 0 && (a.nphase != 1 || (a.NL == 1 && a.resid != nullptr))) return false;
-  if (a.seg_out != nullptr && (a.seg_key == nullptr || a.seg_rowptr == nullptr || a.seg_part == nullptr || a.n_post > 0)) return false;
-  for (int u = 0; u < G; ++u)
-    if (a.wpk[u] == nullptr) return false;
-  return true;
-}
-template <int TERMS, int NW, int ACT, class SH = ShDyn>
-static int set_fwd_x6_attr() {
-  return hipFuncSetAttribute((const void*)k_mlp_fwd_x6<TERMS, NW, ACT, SH>, hipFuncAttributeMaxDynamicSharedMemorySize, X6_FWD_LDS_BYTES(NW)) != hipSuccess;
-}
-// The static-shape instantiations (mgn_x6.inc: unrolled unit loop, untracked operand loads) take a launch only
-// when it matches their shape field by field; MGN_X6_STATIC=0 keeps every launch on the dynamic kernel (A/B).
-static int fwd_static_shape(const mgn_mlp_fwd_args& a) {
-  const char* env = getenv("MGN_X6_STATIC");  // read per launch: the cross-check test flips it inside one process
-  const int mode = env != nullptr ? atoi(env) : 1;  // 0 none, 2 edge only
-  if (mode == 0 || a.act != MGN_ACT_RELU || a.NL != 4 || a.resid == nullptr || a.scale == nullptr) return 0;
-  if (a.nphase == 1 && a.n_add == 2 && a.n_post == 0 && a.idx[0] == nullptr && a.add_idx[0] != nullptr && a.add_idx[1] != nullptr &&
-      a.seg_out != nullptr && a.seg_key == a.add_idx[0])
-    return 1;  // ShEdge
-  // ShNode (node update): only where a workgroup runs several tiles.  On a one-tile launch (30 k node rows = 472
-  // tiles) its 28 straight-line quarters are instruction fetch with no reuse: 64 us against 46 us for the rolled loop.
-  if (mode != 2 && a.nphase == 2 && a.n_add == 0 && a.idx[0] == nullptr && a.idx[1] == nullptr && a.seg_out == nullptr && a.M >= 4 * 512 * 64) {
-    if (a.n_post == 2) return 2;  // ShNode<2>
-    if (a.n_post == 0) return 3;  // ShNode<0>
-  }
-  return 0;
-}
-
-// The ping-pong edge update (mgn_pp.inc) takes a ShEdge launch when it is fp32-grade, its four units lie back to back,
-// the messages are not written (fused aggregation only), the saves are all there or all absent, and every CU gets at
-// least two 128-row tiles (on a one-tile launch the alternation only doubles the tile's latency).
-// MGN_PP unset: INFERENCE-mode launches only (no saves: measured 127-130 us against 132-145 us at the bench size; the
-// training-mode instance is slower than the x6 kernel); 0: off; 1: both modes; 2: both modes at any size (tests).
-static bool fwd_pp_ok(const mgn_mlp_fwd_args& a) {
-  const char* env = getenv("MGN_PP");
-  const int mode = (env == nullptr) ? -1 : atoi(env);
-  if (mode == 0) return false;
-  const int64_t min_rows = (mode == 2) ? 1 : 2 * 128 * 256;
-  if (a.precision != 0 || a.y_out != nullptr || a.M < min_rows || a.M * 512 >= (int64_t)1 << 32) return false;  // (32-bit row offsets)
-  for (int u = 1; u < 4; ++u)
-    if ((const char*)a.wpk[u] != (const char*)a.wpk[0] + (size_t)u * MGN_WPACK_BYTES) return false;
-  const bool all = a.saveU && a.saveR && a.saveH[0] && a.saveH[1] && a.saveH[2] && a.saveM[0] && a.saveM[1] && a.saveM[2];
-  const bool none = !a.saveU && !a.saveR && !a.saveH[0] && !a.saveH[1] && !a.saveH[2] && !a.saveM[0] && !a.saveM[1] && !a.saveM[2];
-  if (mode < 0 && !none) return false;
-  // rows past M are computed as copies of row M - 1 and stored there again: the outputs must alias no input
-  return (all || none) && a.resid != nullptr && a.scale != nullptr && a.out != a.resid && a.out != a.src[0];
-}
-
-// The register-resident-weights edge update (mgn_ppr.inc) takes a ShEdge launch under the ping-pong kernel's conditions (fp32-grade,
-// units back to back, no message output, saves all there or all absent, outputs alias no input) from 65 536 rows (every CU gets
-// >= 8 groups of 32 rows: below that the two-slot lag of its second half is not amortised).  MGN_PPR: unset = on, both modes;
-// 0 = off; 2 = at any size (tests); MGN_PPR_XCD=0: plain hand-out of the groups instead of XCD by XCD (A/B).
-// Its gathers address Pd / Ps rows with 32-bit byte offsets (row * 512): both sources must have a known row count below 2^23.
-static bool fwd_ppr_ok(const mgn_mlp_fwd_args& a) {
-  const char* env = getenv("MGN_PPR");
-  const int mode = (env == nullptr) ? 1 : atoi(env);
-  if (mode == 0) return false;
-  const int64_t min_rows = (mode == 2) ? 1 : 65536;
-  if (a.precision != 0 || a.y_out != nullptr || a.M < min_rows || a.M * 512 >= (int64_t)1 << 32) return false;  // (32-bit row offsets)
-  for (int q = 0; q < 2; ++q)
-    if (a.add_rows[q] <= 0 || a.add_rows[q] * 512 >= (int64_t)1 << 32) return false;
-  for (int u = 1; u < 4; ++u)
-    if ((const char*)a.wpk[u] != (const char*)a.wpk[0] + (size_t)u * MGN_WPACK_BYTES) return false;
-  const bool all = a.saveU && a.saveR && a.saveH[0] && a.saveH[1] && a.saveH[2] && a.saveM[0] && a.saveM[1] && a.saveM[2];
-  const bool none = !a.saveU && !a.saveR && !a.saveH[0] && !a.saveH[1] && !a.saveH[2] && !a.saveM[0] && !a.saveM[1] && !a.saveM[2];
-  // rows past M are computed as copies of row M - 1 and stored there again: the outputs must alias no input
-  return (all || none) && a.resid != nullptr && a.scale != nullptr && a.out != a.resid && a.out != a.src[0];
-}
-
-template <int HB>
-static int launch_fwd(const mgn_mlp_fwd_args& a, hipStream_t s) {
-  const bool ragged = fwd_ragged(a);
-  const MlpPlan p = plan_mlp(a.M, a.H, a.NL, ragged, false, a.act);
-  if (p.lds && fwd_x6(a)) {
-    // 4 waves per workgroup at every M (8-wave workgroups, one per CU, are the MGN_NW=8 override)
-    int nw = 4;
-    bool nw6 = false;  // MGN_NW=6: the three-waves-per-SIMD instance of the edge update (experiment)
-    if (const char* e = getenv("MGN_NW")) {
-      nw = (atoi(e) == 8) ? 8 : 4;
-      nw6 = atoi(e) == 6;
-    }
-    if (a.seg_out != nullptr) nw = 4;  // (the 8-wave instance has no fused segment sum)
-    const bool silu = (a.act == MGN_ACT_SILU);
-    if (silu) nw = 4;  // the SiLU variant is built for 4-wave workgroups only
-    static thread_local bool attr_done = false;
-    if (!attr_done) {
-      if (set_fwd_x6_attr<6, 4, 0>() || set_fwd_x6_attr<1, 4, 0>() || set_fwd_x6_attr<6, 8, 0>() || set_fwd_x6_attr<1, 8, 0>() ||
-          set_fwd_x6_attr<6, 4, 1>() || set_fwd_x6_attr<1, 4, 1>() || set_fwd_x6_attr<6, 4, 0, ShEdge>() ||
-          set_fwd_x6_attr<6, 4, 0, ShNode<2>>() || set_fwd_x6_attr<6, 4, 0, ShNode<0>>() || set_fwd_x6_attr<1, 4, 0, ShEdge>() ||
-          set_fwd_x6_attr<1, 4, 0, ShNode<2>>() || set_fwd_x6_attr<1, 4, 0, ShNode<0>>() || set_fwd_x6_attr<6, 6, 0, ShEdge>())
-        return 1;
-      attr_done = true;
-    }
-    const int rows = 16 * nw;
-    unsigned grid = (unsigned)((a.M + rows - 1) / rows);
-    const unsigned cap = (nw == 8) ? 256u : 512u;
-    if (grid > cap) grid = cap;
-    if (const char* e = getenv("MGN_GRID")) {  // occupancy experiments: fewer persistent workgroups
-      if (atoi(e) > 0 && (unsigned)atoi(e) < grid) grid = (unsigned)atoi(e);
-    }
-    const int shape = (nw == 4 && !silu) ? fwd_static_shape(a) : 0;
-    if (shape == 1 && !nw6 && fwd_ppr_ok(a)) {
-      static thread_local bool ppr_attr = false;
-      if (!ppr_attr) {
-        if (hipFuncSetAttribute((const void*)k_edge_fwd_ppr<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, PPR_LDS_BYTES) != hipSuccess ||
-            hipFuncSetAttribute((const void*)k_edge_fwd_ppr<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, PPR_LDS_BYTES) != hipSuccess ||
-            hipFuncSetAttribute((const void*)k_edge_fwd_ppr<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, PPR_LDS_BYTES) != hipSuccess ||
-            hipFuncSetAttribute((const void*)k_edge_fwd_ppr<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, PPR_LDS_BYTES) != hipSuccess)
-          return 1;
-        ppr_attr = true;
-      }
-      const int64_t ngroups = ((a.M + 15) / 16 + PPR_R - 1) / PPR_R;
-      unsigned gp = (ngroups < 256) ? (unsigned)ngroups : 256u;
-      const char* ex = getenv("MGN_PPR_XCD");
-      const bool xcd = ex == nullptr || atoi(ex) != 0;
-      if (a.saveU != nullptr) {
-        if (xcd) hipLaunchKernelGGL((k_edge_fwd_ppr<true, true>), dim3(gp), dim3(512), PPR_LDS_BYTES, s, a);
-        else hipLaunchKernelGGL((k_edge_fwd_ppr<true, false>), dim3(gp), dim3(512), PPR_LDS_BYTES, s, a);
-      } else {
-        if (xcd) hipLaunchKernelGGL((k_edge_fwd_ppr<false, true>), dim3(gp), dim3(512), PPR_LDS_BYTES, s, a);
-        else hipLaunchKernelGGL((k_edge_fwd_ppr<false, false>), dim3(gp), dim3(512), PPR_LDS_BYTES, s, a);
-      }
-      return 0;
-    }
-    if (shape == 1 && !nw6 && fwd_pp_ok(a)) {
-      static thread_local bool pp_attr = false;
-      if (!pp_attr) {
-        if (hipFuncSetAttribute((const void*)k_edge_fwd_pp<true>, hipFuncAttributeMaxDynamicSharedMemorySize, PP_LDS_BYTES) != hipSuccess ||
-            hipFuncSetAttribute((const void*)k_edge_fwd_pp<false>, hipFuncAttributeMaxDynamicSharedMemorySize, PP_LDS_BYTES) != hipSuccess)
-          return 1;
-        pp_attr = true;
-      }
-      unsigned gp = (unsigned)((a.M + 127) / 128);
-      if (gp > 256u) gp = 256u;
-      if (a.saveU != nullptr)
-        hipLaunchKernelGGL((k_edge_fwd_pp<true>), dim3(gp), dim3(512), PP_LDS_BYTES, s, a);
-      else
-        hipLaunchKernelGGL((k_edge_fwd_pp<false>), dim3(gp), dim3(512), PP_LDS_BYTES, s, a);
-      return 0;
-    }
-    if (shape == 1 && nw6 && a.precision == 0) {
-      unsigned g6 = (unsigned)((a.M + 95) / 96);
-      if (g6 > 512u) g6 = 512u;
-      hipLaunchKernelGGL((k_mlp_fwd_x6<6, 6, 0, ShEdge>), dim3(g6), dim3(384), X6_FWD_LDS_BYTES(6), s, a);
-    } else if (shape == 1) {
-      if (a.precision >= 1)
-        hipLaunchKernelGGL((k_mlp_fwd_x6<1, 4, 0, ShEdge>), dim3(grid), dim3(256), X6_FWD_LDS_BYTES(4), s, a);
-      else
-        hipLaunchKernelGGL((k_mlp_fwd_x6<6, 4, 0, ShEdge>), dim3(grid), dim3(256), X6_FWD_LDS_BYTES(4), s, a);
-    } else if (shape == 2) {
-      if (a.precision >= 1)
-        hipLaunchKernelGGL((k_mlp_fwd_x6<1, 4, 0, ShNode<2>>), dim3(grid), dim3(256), X6_FWD_LDS_BYTES(4), s, a);
-      else
-        hipLaunchKernelGGL((k_mlp_fwd_x6<6, 4, 0, ShNode<2>>), dim3(grid), dim3(256), X6_FWD_LDS_BYTES(4), s, a);
-    } else if (shape == 3) {
-      if (a.precision >= 1)
-        hipLaunchKernelGGL((k_mlp_fwd_x6<1, 4, 0, ShNode<0>>), dim3(grid), dim3(256), X6_FWD_LDS_BYTES(4), s, a);
-      else
-        hipLaunchKernelGGL((k_mlp_fwd_x6<6, 4, 0, ShNode<0>>), dim3(grid), dim3(256), X6_FWD_LDS_BYTES(4), s, a);
-    } else if (silu) {
-      if (a.precision >= 1)
-        hipLaunchKernelGGL((k_mlp_fwd_x6<1, 4, 1>), dim3(grid), dim3(256), X6_FWD_LDS_BYTES(4), s, a);
-      else
-        hipLaunchKernelGGL((k_mlp_fwd_x6<6, 4, 1>), dim3(grid), dim3(256), X6_FWD_LDS_BYTES(4), s, a);
-    } else if (nw == 8) {
-      if (a.precision >= 1)
-        hipLaunchKernelGGL((k_mlp_fwd_x6<1, 8, 0>), dim3(grid), dim3(512), X6_FWD_LDS_BYTES(8), s, a);
-      else
-        hipLaunchKernelGGL((k_mlp_fwd_x6<6, 8, 0>), dim3(grid), dim3(512), X6_FWD_LDS_BYTES(8), s, a);
-    } else {
-      if (a.precision >= 1)
-        hipLaunchKernelGGL((k_mlp_fwd_x6<1, 4, 0>), dim3(grid), dim3(256), X6_FWD_LDS_BYTES(4), s, a);
-      else
-        hipLaunchKernelGGL((k_mlp_fwd_x6<6, 4, 0>), dim3(grid), dim3(256), X6_FWD_LDS_BYTES(4), s, a);
-    }
-    return 0;
-  }
-  if (p.lds) {
-    if (p.mt == 2) {
-      if (set_smem(k_mlp_fwd_lds<2>)) return 1;
-      hipLaunchKernelGGL((k_mlp_fwd_lds<2>), dim3(p.grid), dim3(256), p.smem, s, a);
-    } else {
-      if (set_smem(k_mlp_fwd_lds<1>)) return 1;
-      hipLaunchKernelGGL((k_mlp_fwd_lds<1>), dim3(p.grid), dim3(256), p.smem, s, a);
-    }
-    return 0;
-  }
-  if (ragged) {  // encoders / decoder: guarded generic first / last layer
-    if (p.mt == 2)
-      hipLaunchKernelGGL((k_mlp_fwd<HB, 2, true>), dim3(p.grid), dim3(256), 0, s, a);
-    else
-      hipLaunchKernelGGL((k_mlp_fwd<HB, 1, true>), dim3(p.grid), dim3(256), 0, s, a);
-  } else {
-    if (p.mt == 2)
-      hipLaunchKernelGGL((k_mlp_fwd<HB, 2, false>), dim3(p.grid), dim3(256), 0, s, a);
-    else
-      hipLaunchKernelGGL((k_mlp_fwd<HB, 1, false>), dim3(p.grid), dim3(256), 0, s, a);
-  }
-  return 0;
-}
-
-static bool bwd_x6(const mgn_mlp_bwd_args& a) {
-  if (a.wpk[0] == nullptr || getenv("MGN_FP32_MFMA") != nullptr) return false;
-  const int G = a.n_front + a.NL - 1 + a.n_din;
-  if (G > 8 || G < 1 || a.n_front < 0 || a.n_front > MGN_MAX_PHASES) return false;
-  if (a.n_front > 0 && a.dOut2 != nullptr) return false;
-  for (int u = 0; u < G; ++u)
-    if (a.wpk[u] == nullptr) return false;
-  if (a.seg_out != nullptr && (a.seg_key == nullptr || a.seg_rowptr == nullptr || a.seg_part == nullptr || a.dZ[0] == nullptr ||
-                               a.n_front > 0 || a.act != MGN_ACT_RELU || a.precision != 0 || a.NL < 2))
-    return false;
-  if (a.act == MGN_ACT_SILU) {
-    if (a.n_front > 0 || (a.n_din == 0 && a.dOut2 != nullptr)) return false;  // see k_mlp_bwd_x6: pd2 carries the z rows
-    for (int l = 1; l < a.NL; ++l)
-      if (a.Zs[l - 1] == nullptr) return false;
-    return true;
-  }
-  for (int l = 1; l < a.NL; ++l)
-    if (a.Ms[l - 1] == nullptr) return false;  // the split-bf16 chain reads ReLU masks as bits
-  return true;
-}
-
-// The register-resident-weights edge backward chain (mgn_ppr.inc) takes an SbEdge launch when it is fp32-grade, its four units lie
-// back to back, only dscale is asked for as a column sum, every dZ is written as fp32 rows and the outputs alias no input (rows past
-// M are computed as copies of row M - 1 and stored there again), from 65 536 rows.  MGN_PPR as for the forward kernel; MGN_PPR_BWD=0
-// keeps the x6 chain (A/B).  Its gather of dOut2 uses 32-bit byte offsets (row * 512): dOut2 needs a known row count below 2^23.
-static bool bwd_ppr_ok(const mgn_mlp_bwd_args& a) {
-  const char* env = getenv("MGN_PPR");
-  const int mode = (env == nullptr) ? 1 : atoi(env);
-  const char* eb = getenv("MGN_PPR_BWD");
-  if (mode == 0 || (eb != nullptr && atoi(eb) == 0)) return false;
-  const int64_t min_rows = (mode == 2) ? 1 : 65536;
-  if (a.precision != 0 || a.M < min_rows || a.M * 512 >= (int64_t)1 << 32 || a.dscale == nullptr) return false;
-  if (a.dOut2_rows <= 0 || a.dOut2_rows * 512 >= (int64_t)1 << 32) return false;
-  for (int u = 1; u < 4; ++u)
-    if ((const char*)a.wpk[u] != (const char*)a.wpk[0] + (size_t)u * MGN_WPACK_BYTES) return false;
-  for (int l = 0; l < 4; ++l)
-    if (a.db[l] != nullptr || a.dZ[l] == nullptr) return false;
-  if (a.dIn[0] == nullptr || a.Ms[0] == nullptr || a.Ms[1] == nullptr || a.Ms[2] == nullptr) return false;
-  const void* ins[4] = {a.dOut, a.U, a.din_resid[0], a.dOut2};
-  const void* outs[5] = {a.dZ[0], a.dZ[1], a.dZ[2], a.dZ[3], a.dIn[0]};
-  for (const void* o : outs)
-    for (const void* i : ins)
-      if (o == i) return false;
-  return true;
-}
-
-template <int HB>
-static int launch_bwd(const mgn_mlp_bwd_args& a, hipStream_t s) {
-  MlpPlan p = plan_mlp(a.M, a.H, a.NL, a.out_w != a.H || a.n_din > 1, true, a.act);
-  if (p.lds && bwd_x6(a)) {
-    static thread_local bool attr_done = false;
-    if (!attr_done) {
-      const int lds = X6_BWD_LDS_BYTES(LDS_MAX_NL + 1);
-      if (hipFuncSetAttribute((const void*)k_mlp_bwd_x6<6, false, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess ||
-          hipFuncSetAttribute((const void*)k_mlp_bwd_x6<1, false, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess ||
-          hipFuncSetAttribute((const void*)k_mlp_bwd_x6<6, true, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess ||
-          hipFuncSetAttribute((const void*)k_mlp_bwd_x6<1, true, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess ||
-          hipFuncSetAttribute((const void*)k_mlp_bwd_x6<6, false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess ||
-          hipFuncSetAttribute((const void*)k_mlp_bwd_x6<1, false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess ||
-          hipFuncSetAttribute((const void*)k_mlp_bwd_x6<6, false, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess ||
-          hipFuncSetAttribute((const void*)k_mlp_bwd_x6<6, false, 0, false, SbEdge>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess ||
-          hipFuncSetAttribute((const void*)k_mlp_bwd_x6<1, false, 0, false, SbEdge>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
-        return 1;
-      attr_done = true;
-    }
-    int nused = (a.scale != nullptr && a.dscale != nullptr) ? 1 : 0;
-    for (int l = 0; l < a.NL; ++l) nused += (a.db[l] != nullptr) ? 1 : 0;
-    const size_t lds = X6_BWD_LDS_BYTES(nused);
-    const bool front = a.n_front > 0;
-    const char* st_env = getenv("MGN_X6_STATIC");
-    const bool static_off = st_env != nullptr && atoi(st_env) == 0;
-    // static-shape instantiation (mgn_x6.inc, SbEdge): the edge chain of a round, matched field by field
-    const bool sb_edge = !static_off && !front && a.seg_out == nullptr && a.act == MGN_ACT_RELU && a.NL == 4 &&
-                         a.n_din == 1 && a.din_resid[0] != nullptr && a.scale != nullptr && a.R != nullptr && a.U != nullptr &&
-                         a.dOut2 != nullptr && a.idx2 != nullptr;
-    if (sb_edge && bwd_ppr_ok(a)) {
-      static thread_local bool ppr_attr = false;
-      if (!ppr_attr) {
-        if (hipFuncSetAttribute((const void*)k_edge_bwd_ppr<true>, hipFuncAttributeMaxDynamicSharedMemorySize, PPB_LDS_BYTES) != hipSuccess ||
-            hipFuncSetAttribute((const void*)k_edge_bwd_ppr<false>, hipFuncAttributeMaxDynamicSharedMemorySize, PPB_LDS_BYTES) != hipSuccess)
-          return 1;
-        ppr_attr = true;
-      }
-      const int64_t ngroups = ((a.M + 15) / 16 + PPR_R - 1) / PPR_R;
-      unsigned gp = (ngroups < 256) ? (unsigned)ngroups : 256u;
-      if (gp > p.grid) gp = p.grid;  // (the column reduction reads p.grid partials: never more workgroups than that)
-      const char* ex = getenv("MGN_PPR_XCD");
-      if (ex == nullptr || atoi(ex) != 0)
-        hipLaunchKernelGGL((k_edge_bwd_ppr<true>), dim3(gp), dim3(512), PPB_LDS_BYTES, s, a, (int)p.grid);
-      else
-        hipLaunchKernelGGL((k_edge_bwd_ppr<false>), dim3(gp), dim3(512), PPB_LDS_BYTES, s, a, (int)p.grid);
-    } else if (sb_edge) {
-      if (a.precision >= 1)
-        hipLaunchKernelGGL((k_mlp_bwd_x6<1, false, 0, false, SbEdge>), dim3(p.grid), dim3(256), lds, s, a);
-      else
-        hipLaunchKernelGGL((k_mlp_bwd_x6<6, false, 0, false, SbEdge>), dim3(p.grid), dim3(256), lds, s, a);
-    } else if (a.seg_out != nullptr) {
-      hipLaunchKernelGGL((k_mlp_bwd_x6<6, false, 0, true>), dim3(p.grid), dim3(256), lds, s, a);
-    } else if (a.act == MGN_ACT_SILU) {
-      if (a.precision >= 1)
-        hipLaunchKernelGGL((k_mlp_bwd_x6<1, false, 1>), dim3(p.grid), dim3(256), lds, s, a);
-      else
-        hipLaunchKernelGGL((k_mlp_bwd_x6<6, false, 1>), dim3(p.grid), dim3(256), lds, s, a);
-    } else if (a.precision >= 1) {
-      if (front)
-        hipLaunchKernelGGL((k_mlp_bwd_x6<1, true, 0>), dim3(p.grid), dim3(256), lds, s, a);
-      else
-        hipLaunchKernelGGL((k_mlp_bwd_x6<1, false, 0>), dim3(p.grid), dim3(256), lds, s, a);
-    } else {
-      if (front)
-        hipLaunchKernelGGL((k_mlp_bwd_x6<6, true, 0>), dim3(p.grid), dim3(256), lds, s, a);
-      else
-        hipLaunchKernelGGL((k_mlp_bwd_x6<6, false, 0>), dim3(p.grid), dim3(256), lds, s, a);
-    }
-    return 0;
-  }
-  if (p.lds) {
-    if (p.mt == 2) {
-      if (set_smem(k_mlp_bwd_lds<2>)) return 1;
-      hipLaunchKernelGGL((k_mlp_bwd_lds<2>), dim3(p.grid), dim3(256), p.smem, s, a);
-    } else {
-      if (set_smem(k_mlp_bwd_lds<1>)) return 1;
-      hipLaunchKernelGGL((k_mlp_bwd_lds<1>), dim3(p.grid), dim3(256), p.smem, s, a);
-    }
-    return 0;
-  }
-  if (a.out_w != a.H) {
-    if (p.mt == 2)
-      hipLaunchKernelGGL((k_mlp_bwd<HB, 2, true>), dim3(p.grid), dim3(256), 0, s, a);
-    else
-      hipLaunchKernelGGL((k_mlp_bwd<HB, 1, true>), dim3(p.grid), dim3(256), 0, s, a);
-  } else {
-    if (p.mt == 2)
-      hipLaunchKernelGGL((k_mlp_bwd<HB, 2, false>), dim3(p.grid), dim3(256), 0, s, a);
-    else
-      hipLaunchKernelGGL((k_mlp_bwd<HB, 1, false>), dim3(p.grid), dim3(256), 0, s, a);
-  }
-  return 0;
-}
-
 extern "C" {
 
 int mgn_version(void) { return 136; }
@@ -2704,6 +2315,426 @@ int mgn_segsum2_b16(const uint16_t* src, const int32_t* rowptr0, const int32_t* 
   return check_launch("mgn_segsum2_b16");
 }
 
+}  // extern "C"
+
+// ============================================================================ MLP and weight-gradient routing
+// mgn_mlp_fwd, mgn_mlp_bwd, mgn_colred_batch and mgn_wgrad_p decide a launch in steps that do not mix: read_switches() reads
+// the environment once per call; route_fwd / route_bwd / route_wgrad are pure functions of (arguments, switches) that name a
+// row of kKernels with its grid, block and LDS bytes and the facts the refusals test; the entry point refuses, reserves LDS
+// (reserve_lds) and launches the row.  tests/test_mlp_routes_host.py runs the entry points on the host, without a device, and
+// compares every route and refusal with tests/mlp_routes_expected.txt.
+
+// ---------------------------------------------------------------------------------------- switches
+// Every MGN_* environment switch of this unit and the .inc files it includes: one field each, filled by read_switches() on
+// every call (the parity tests flip switches inside one process) and nowhere else.  "set" = present with any value.
+struct Switches {
+  bool no_lds;               // MGN_NO_LDS set: no LDS-weight kernel -- H = 128 full-width launches and full 128 x 128 weight-gradient
+                             // jobs run on the generic kernels (and with the LDS path the packed split-bf16 path is off)
+  int mt;                    // MGN_MT: 16-row tiles per wave of the generic and LDS kernels: "2" = 2, any other value = 1; 0 = unset (by M)
+  int grid;                  // MGN_GRID=n > 0: at most n persistent workgroups of a forward LDS / x6 launch (occupancy experiments); 0 = none
+  bool fp32_mfma;            // MGN_FP32_MFMA set: the exact-fp32 MFMA kernels instead of the packed split-bf16 path (cross-check; ReLU only)
+  int x6_static;             // MGN_X6_STATIC: static-shape instantiations of the x6 chain kernels (mgn_x6.inc: unrolled unit loop, untracked
+                             // operand loads): 0 none (A/B), 2 the edge update only, any other value and unset (1) all
+  int pp;                    // MGN_PP: the ping-pong edge forward (mgn_pp.inc) where MGN_PPR does not take the launch: unset (-1)
+                             // INFERENCE-mode launches only (no saves: measured 127-130 us against 132-145 us at the bench size; the
+                             // training-mode instance is slower than the x6 kernel); 0 off; 1 both modes; 2 both at any size (tests)
+  int ppr;                   // MGN_PPR: the register-resident-weights edge kernels (mgn_ppr.inc): unset (1) on from 65 536 rows, both
+                             // modes; 0 off; 2 at any size (tests)
+  bool ppr_xcd;              // MGN_PPR_XCD=0 clears it: plain hand-out of the ppr row groups instead of XCD by XCD (A/B)
+  bool ppr_bwd;              // MGN_PPR_BWD=0 clears it: the backward keeps the x6 chain (A/B)
+  int nw;                    // MGN_NW: waves per workgroup of the x6 forward: 8 = one 8-wave workgroup per CU; 6 = the three-waves-per-SIMD
+                             // instance of the edge update (experiment); any other value and unset: 4
+  int wgrad_generic_budget;  // MGN_WGRAD_GENERIC_BUDGET=n, 64 <= n <= 1024: workgroups of a pass-1 weight-gradient launch; else 512
+  bool wgrad_no_row64;       // MGN_WGRAD_NO_ROW64 set: jobs up to 64 x 64 on the generic kernel instead of the row-vector one (A/B)
+  bool wgrad_pc;             // MGN_WGRAD_PC=0 clears it: fp32-row full jobs on k_wgrad_x6<6> instead of the producer / consumer kernel
+  bool wgrad_no_interleave;  // MGN_WGRAD_NO_INTERLEAVE set: contiguous workgroup ranges per job instead of the XCD-interleaved order
+  bool wgrad_row64_exact;    // MGN_WGRAD_ROW64_EXACT set: row-vector weight gradients on exact-fp32 MFMA instead of k_wgrad_row64x6
+};
+static Switches read_switches() {
+  const auto set = [](const char* name) { return getenv(name) != nullptr; };
+  const auto num = [](const char* name, int unset) {
+    const char* e = getenv(name);
+    return e != nullptr ? atoi(e) : unset;
+  };
+  Switches w;
+  w.no_lds = set("MGN_NO_LDS");
+  const int mt = num("MGN_MT", 2), grid = num("MGN_GRID", 0);
+  w.mt = !set("MGN_MT") ? 0 : mt == 2 ? 2 : 1;
+  w.grid = grid > 0 ? grid : 0;
+  w.fp32_mfma = set("MGN_FP32_MFMA");
+  w.x6_static = num("MGN_X6_STATIC", 1);
+  w.pp = num("MGN_PP", -1);
+  w.ppr = num("MGN_PPR", 1);
+  w.ppr_xcd = num("MGN_PPR_XCD", 1) != 0;
+  w.ppr_bwd = num("MGN_PPR_BWD", 1) != 0;
+  w.nw = num("MGN_NW", 4);
+  const int budget = num("MGN_WGRAD_GENERIC_BUDGET", 0);
+  w.wgrad_generic_budget = (budget >= 64 && budget <= 1024) ? budget : 512;
+  w.wgrad_no_row64 = set("MGN_WGRAD_NO_ROW64");
+  w.wgrad_pc = num("MGN_WGRAD_PC", 1) != 0;
+  w.wgrad_no_interleave = set("MGN_WGRAD_NO_INTERLEAVE");
+  w.wgrad_row64_exact = set("MGN_WGRAD_ROW64_EXACT");
+  return w;
+}
+
+// ---------------------------------------------------------------------------------------- kernel table
+// Every kernel these entry points launch, one row each.  The rows stand in the order the device code object has always held
+// the kernels (hipcc emits an instantiation where the host code first names it): reordering rows, or naming one of these
+// kernels above this table, changes the shipped binary (tools/device_code_hash.py).  A new kernel gets a new row at the end
+// of its group's enumerator range or at the end of the table, a branch in its route function and a line in
+// tests/mlp_routes_expected.txt.
+enum KernelSig { SIG_FWD, SIG_BWD, SIG_BWD_PPR, SIG_WGRAD, SIG_COUNT };
+struct KernelRow {
+  const char* name;  // the instantiation as its row spells it
+  const void* fn;    // host handle, type-checked against `sig` where the row is written
+  int sig;           // KernelSig: the argument list
+  int lds;           // dynamic LDS bytes to reserve before the first launch (0: the kernel stays below the default limit)
+};
+#define KROW(sig, type, lds, ...) {#__VA_ARGS__, (const void*)static_cast<type>(__VA_ARGS__), sig, lds}
+#define FWD(lds, ...) KROW(SIG_FWD, void (*)(mgn_mlp_fwd_args), lds, __VA_ARGS__)
+#define BWD(lds, ...) KROW(SIG_BWD, void (*)(mgn_mlp_bwd_args), lds, __VA_ARGS__)
+#define BWD_PPR(lds, ...) KROW(SIG_BWD_PPR, void (*)(mgn_mlp_bwd_args, int), lds, __VA_ARGS__)
+#define WGRAD(lds, ...) KROW(SIG_WGRAD, void (*)(WgradLaunch), lds, __VA_ARGS__)
+#define GEN_LDS_RESERVE (2 * WBUF_BYTES + 4 * 7 * 128 * 4) /* k_mlp_fwd_lds / k_mlp_bwd_lds at their deepest */
+#define X6_BWD_RESERVE X6_BWD_LDS_BYTES(LDS_MAX_NL + 1)
+#define GENERIC_ROWS(ROW, k)                                                                                                      \
+  ROW(0, k<8,2,true>), ROW(0, k<8,1,true>), ROW(0, k<8,2,false>), ROW(0, k<8,1,false>), ROW(0, k<4,2,true>), ROW(0, k<4,1,true>), \
+  ROW(0, k<4,2,false>), ROW(0, k<4,1,false>), ROW(0, k<2,2,true>), ROW(0, k<2,1,true>), ROW(0, k<2,2,false>), ROW(0, k<2,1,false>), \
+  ROW(0, k<1,2,true>), ROW(0, k<1,1,true>), ROW(0, k<1,2,false>), ROW(0, k<1,1,false>)
+// first row of each group; what is added to it stands beside the group's rows
+enum Kernel {
+  K_FWD_PPR = 0, K_FWD_PP = 4, K_FWD_NW6 = 6, K_FWD_EDGE = 7, K_FWD_NODE2 = 9, K_FWD_NODE0 = 11, K_FWD_SILU = 13, K_FWD_NW8_BF16 = 15,
+  K_FWD_LDS = 16, K_FWD_GEN = 18, K_BWD_FRONT = 34, K_BWD_SILU = 36, K_BWD_SEG = 38, K_BWD_EDGE = 39, K_BWD_PPR = 41, K_BWD_LDS = 43,
+  K_BWD_GEN = 45, K_WGRAD_X6 = 61, K_WGRAD_ROW64_BF16 = 63, K_WGRAD_ROW64X6 = 67, K_WGRAD_ROW64 = 69, K_WGRAD_GEN = 70, K_WGRAD_RED = 74,
+  K_FWD_DYN = 76, K_FWD_NW8 = 78, K_BWD_DYN = 79, K_WGRAD_LDS = 81, K_WGRAD_PC = 82, K_COUNT = 83
+};
+static const KernelRow kKernels[] = {
+    // K_FWD_PPR + (no saves ? 1 : 0) + (plain hand-out ? 2 : 0)
+    FWD(PPR_LDS_BYTES, k_edge_fwd_ppr<true,true>), FWD(PPR_LDS_BYTES, k_edge_fwd_ppr<false,true>),
+    FWD(PPR_LDS_BYTES, k_edge_fwd_ppr<true,false>), FWD(PPR_LDS_BYTES, k_edge_fwd_ppr<false,false>),
+    // K_FWD_PP + (no saves ? 1 : 0)
+    FWD(PP_LDS_BYTES, k_edge_fwd_pp<true>), FWD(PP_LDS_BYTES, k_edge_fwd_pp<false>),
+    // K_FWD_NW6; then K_FWD_EDGE, _NODE2, _NODE0, _SILU + (fp32-grade ? 1 : 0): the one-term bf16 instance comes first
+    FWD(X6_FWD_LDS_BYTES(6), k_mlp_fwd_x6<6,6,0,ShEdge>),
+    FWD(X6_FWD_LDS_BYTES(4), k_mlp_fwd_x6<1,4,0,ShEdge>), FWD(X6_FWD_LDS_BYTES(4), k_mlp_fwd_x6<6,4,0,ShEdge>),
+    FWD(X6_FWD_LDS_BYTES(4), k_mlp_fwd_x6<1,4,0,ShNode<2>>), FWD(X6_FWD_LDS_BYTES(4), k_mlp_fwd_x6<6,4,0,ShNode<2>>),
+    FWD(X6_FWD_LDS_BYTES(4), k_mlp_fwd_x6<1,4,0,ShNode<0>>), FWD(X6_FWD_LDS_BYTES(4), k_mlp_fwd_x6<6,4,0,ShNode<0>>),
+    FWD(X6_FWD_LDS_BYTES(4), k_mlp_fwd_x6<1,4,1>), FWD(X6_FWD_LDS_BYTES(4), k_mlp_fwd_x6<6,4,1>),
+    FWD(X6_FWD_LDS_BYTES(8), k_mlp_fwd_x6<1,8,0>),  // K_FWD_NW8_BF16 (fp32-grade: K_FWD_NW8 below)
+    // K_FWD_LDS + (one tile per wave ? 1 : 0)
+    FWD(GEN_LDS_RESERVE, k_mlp_fwd_lds<2>), FWD(GEN_LDS_RESERVE, k_mlp_fwd_lds<1>),
+    // K_FWD_GEN + 4 * (H = 128, 64, 32, 16 -> 0..3) + (full widths ? 2 : 0) + (one tile per wave ? 1 : 0)
+    GENERIC_ROWS(FWD, k_mlp_fwd),
+    // K_BWD_FRONT, K_BWD_SILU + (bf16 ? 1 : 0); K_BWD_SEG; K_BWD_EDGE + (bf16 ? 1 : 0)
+    BWD(X6_BWD_RESERVE, k_mlp_bwd_x6<6,true,0>), BWD(X6_BWD_RESERVE, k_mlp_bwd_x6<1,true,0>),
+    BWD(X6_BWD_RESERVE, k_mlp_bwd_x6<6,false,1>), BWD(X6_BWD_RESERVE, k_mlp_bwd_x6<1,false,1>),
+    BWD(X6_BWD_RESERVE, k_mlp_bwd_x6<6,false,0,true>),
+    BWD(X6_BWD_RESERVE, k_mlp_bwd_x6<6,false,0,false,SbEdge>), BWD(X6_BWD_RESERVE, k_mlp_bwd_x6<1,false,0,false,SbEdge>),
+    // K_BWD_PPR + (plain hand-out ? 1 : 0): the one kernel with a second argument
+    BWD_PPR(PPB_LDS_BYTES, k_edge_bwd_ppr<true>), BWD_PPR(PPB_LDS_BYTES, k_edge_bwd_ppr<false>),
+    // K_BWD_LDS and K_BWD_GEN as for the forward (ragged: out_w != H)
+    BWD(GEN_LDS_RESERVE, k_mlp_bwd_lds<2>), BWD(GEN_LDS_RESERVE, k_mlp_bwd_lds<1>),
+    GENERIC_ROWS(BWD, k_mlp_bwd),
+    // K_WGRAD_X6 + (bf16 ? 1 : 0)
+    WGRAD(4 * WG_TILE_BYTES, k_wgrad_x6<6>), WGRAD(4 * WG_TILE_BYTES, k_wgrad_x6<1>),
+    // K_WGRAD_ROW64_BF16 + (A and B two-byte rows: 0, A: 1, B: 2, neither: 3)
+    WGRAD(0, k_wgrad_row64<true,true,true>), WGRAD(0, k_wgrad_row64<true,true,false>), WGRAD(0, k_wgrad_row64<true,false,true>),
+    WGRAD(0, k_wgrad_row64<true>),
+    // K_WGRAD_ROW64X6 + (some lane masked ? 1 : 0); K_WGRAD_ROW64 (exact fp32); K_WGRAD_GEN + (H = 128, 64, 32, 16 -> 0..3)
+    WGRAD(0, k_wgrad_row64x6<true>), WGRAD(0, k_wgrad_row64x6<false>), WGRAD(0, k_wgrad_row64<false>),
+    WGRAD(0, k_wgrad<8>), WGRAD(0, k_wgrad<4>), WGRAD(0, k_wgrad<2>), WGRAD(0, k_wgrad<1>),
+    // K_WGRAD_RED + (some job has more than 64 partials ? 1 : 0)
+    WGRAD(0, k_wgrad_red<4>), WGRAD(0, k_wgrad_red<16>),
+    // the dynamic x6 chains: K_FWD_DYN + (bf16 ? 1 : 0); K_FWD_NW8; K_BWD_DYN + (bf16 ? 1 : 0)
+    FWD(X6_FWD_LDS_BYTES(4), k_mlp_fwd_x6<6,4,0>), FWD(X6_FWD_LDS_BYTES(4), k_mlp_fwd_x6<1,4,0>), FWD(X6_FWD_LDS_BYTES(8), k_mlp_fwd_x6<6,8,0>),
+    BWD(X6_BWD_RESERVE, k_mlp_bwd_x6<6,false,0>), BWD(X6_BWD_RESERVE, k_mlp_bwd_x6<1,false,0>),
+    // K_WGRAD_LDS (exact fp32), K_WGRAD_PC (producer / consumer)
+    WGRAD(4 * WG_TILE_BYTES, k_wgrad_lds), WGRAD(WPC_LDS_BYTES, k_wgrad_pc),
+};
+static_assert(sizeof(kKernels) / sizeof(kKernels[0]) == K_COUNT, "kKernels and enum Kernel disagree");
+#undef GENERIC_ROWS
+#undef WGRAD
+#undef BWD_PPR
+#undef BWD
+#undef FWD
+#undef KROW
+
+// Reserves the LDS of every row with row k's argument list, once per thread, before that thread's first launch of any of them
+// that needs it: a whole family at once, so that nothing is reserved for the first time inside a captured region that the
+// eager warm-up steps did not cover.
+static int reserve_lds(int k) {
+  static thread_local bool done[SIG_COUNT];
+  const int sig = kKernels[k].sig;
+  if (kKernels[k].lds == 0 || done[sig]) return 0;
+  for (const KernelRow& r : kKernels)
+    if (r.sig == sig && r.lds > 0 && hipFuncSetAttribute(r.fn, hipFuncAttributeMaxDynamicSharedMemorySize, r.lds) != hipSuccess) return 1;
+  done[sig] = true;
+  return 0;
+}
+// the one launch statement: args are the kernel's arguments, as row k's `sig` lists them
+template <class... A>
+static void launch(int k, dim3 grid, unsigned block, size_t lds, hipStream_t s, const A&... args) {
+  void* argv[] = {(void*)&args...};
+  (void)hipLaunchKernel(kKernels[k].fn, grid, dim3(block), argv, lds, s);  // (check_launch reads the error)
+}
+
+// ---------------------------------------------------------------------------------------- MLP routes
+struct MlpPlan {
+  bool lds;        // LDS-weight kernel: H = 128, full widths, and not GELU (which lives on the generic kernels only)
+  bool lds_shape;  // the same by shape alone, whatever the activation
+  int mt;          // 16-row tiles per wave
+  unsigned grid;   // workgroups
+  size_t smem;     // dynamic LDS bytes
+};
+static MlpPlan plan_mlp(const Switches& w, int64_t M, int H, int NL, bool ragged, bool bwd, int act) {
+  MlpPlan p;
+  p.lds_shape = (H == 128) && !ragged && NL >= (bwd ? 2 : 1) && NL <= LDS_MAX_NL && !w.no_lds;
+  p.lds = p.lds_shape && act != MGN_ACT_GELU;
+  p.mt = (M >= (int64_t)64 * 2048) ? 2 : 1;
+  // measured on MI355X (tools/kbench.py, E = 180k): with LDS-shared weights the forward is
+  // faster at 16 rows per wave (172 VGPRs, no spills: 352 vs 368 us), the backward chain at 32
+  if (p.lds) p.mt = 1;
+  if (w.mt != 0) p.mt = w.mt;
+  const int rows = 64 * p.mt;
+  p.grid = (unsigned)((M + rows - 1) / rows);
+  if (p.lds && p.grid > 512) p.grid = 512;  // persistent: 2 workgroups per CU walk the tiles
+  if (p.lds && !bwd && w.grid > 0 && (unsigned)w.grid < p.grid) p.grid = (unsigned)w.grid;
+  p.smem = p.lds ? (bwd ? (size_t)2 * WBUF_BYTES + 512 + (size_t)4 * (NL + 1) * H * sizeof(float) : (size_t)FWD_LDS_BYTES) : 0;
+  return p;
+}
+// The plan of a backward launch; its grid is the number of partial blocks the launch leaves in red_ws for the column reduction.
+static MlpPlan plan_bwd(const Switches& w, int64_t M, int H, int NL, int out_w, int n_din, int act) {
+  return plan_mlp(w, M, H, NL, out_w != H || n_din > 1, true, act);
+}
+
+struct MlpRoute {
+  int kernel;            // row of kKernels
+  unsigned grid, block;  // workgroups, threads per workgroup
+  size_t lds;            // dynamic LDS bytes of the launch
+  // what the refusals test
+  bool lds_path;         // the H = 128 full-width LDS path takes the launch (MlpPlan::lds)
+  bool lds_shape;        // it would by shape alone (MlpPlan::lds_shape).  The refusals for seg_out, out_relu, SiLU, ldw0 / n_add / n_post,
+                         // two-byte dZ rows and the front stage test this one.  It differs from lds_path only for GELU, and on purpose
+                         // only in that out_relu stays refused at H = 128 with full widths; every other such call is refused as GELU.
+  bool x6;               // the packed split-bf16 path's own conditions hold; it takes the launch when lds_path holds too
+  int nblocks;           // backward: partial blocks in red_ws
+};
+static int generic_row(int H, bool ragged, int mt) { return 4 * (H == 128 ? 0 : H == 64 ? 1 : H == 32 ? 2 : 3) + (ragged ? 0 : 2) + (mt == 2 ? 0 : 1); }
+
+// the four GEMM units of an edge launch lie back to back, as one image of the weight pack
+static bool units_back_to_back(const void* const* wpk) {
+  for (int u = 1; u < 4; ++u)
+    if ((const char*)wpk[u] != (const char*)wpk[0] + (size_t)u * MGN_WPACK_BYTES) return false;
+  return true;
+}
+// the saves of the edge update: 1 all there, 0 all absent, -1 neither
+static int fwd_saves(const mgn_mlp_fwd_args& a) {
+  int n = (a.saveU != nullptr) + (a.saveR != nullptr);
+  for (int l = 0; l < 3; ++l) n += (a.saveH[l] != nullptr) + (a.saveM[l] != nullptr);
+  return n == 8 ? 1 : n == 0 ? 0 : -1;
+}
+
+// split-bf16 kernels: every GEMM unit of the launch comes packed (and the fp32 override is off)
+static bool fwd_x6(const mgn_mlp_fwd_args& a, const Switches& w) {
+  if (a.wpk[0] == nullptr || w.fp32_mfma) return false;
+  const int G = a.nphase + a.NL - 1 + a.n_post;
+  if (G > X6_MAX_UNITS || a.NL > LDS_MAX_NL) return false;
+  // register sharing inside the kernel: gathered adds ride in the next-phase buffer
+  if (a.n_add > 0 && (a.nphase != 1 || (a.NL == 1 && a.resid != nullptr))) return false;
+  if (a.seg_out != nullptr && (a.seg_key == nullptr || a.seg_rowptr == nullptr || a.seg_part == nullptr || a.n_post > 0)) return false;
+  for (int u = 0; u < G; ++u)
+    if (a.wpk[u] == nullptr) return false;
+  return true;
+}
+// The static-shape instantiations take a launch only when it matches their shape field by field: 1 ShEdge, 2 ShNode<2>, 3 ShNode<0>, 0 none.
+static int fwd_static_shape(const mgn_mlp_fwd_args& a, const Switches& w) {
+  if (w.x6_static == 0 || a.act != MGN_ACT_RELU || a.NL != 4 || a.resid == nullptr || a.scale == nullptr) return 0;
+  if (a.nphase == 1 && a.n_add == 2 && a.n_post == 0 && a.idx[0] == nullptr && a.add_idx[0] != nullptr && a.add_idx[1] != nullptr &&
+      a.seg_out != nullptr && a.seg_key == a.add_idx[0])
+    return 1;
+  // ShNode (node update): only where a workgroup runs several tiles.  On a one-tile launch (30 k node rows = 472
+  // tiles) its 28 straight-line quarters are instruction fetch with no reuse: 64 us against 46 us for the rolled loop.
+  if (w.x6_static != 2 && a.nphase == 2 && a.n_add == 0 && a.idx[0] == nullptr && a.idx[1] == nullptr && a.seg_out == nullptr && a.M >= 4 * 512 * 64)
+    return a.n_post == 2 ? 2 : a.n_post == 0 ? 3 : 0;
+  return 0;
+}
+// What the ping-pong (mgn_pp.inc) and the register-resident-weights (mgn_ppr.inc) edge update ask of a ShEdge launch alike: it is
+// fp32-grade, its four units lie back to back, the messages are not written (fused aggregation only), the saves are all there or
+// all absent, it has at least min_rows rows with 32-bit row offsets, and the outputs alias no input (rows past M are computed as
+// copies of row M - 1 and stored there again).
+static bool fwd_edge_stream_ok(const mgn_mlp_fwd_args& a, int64_t min_rows) {
+  return a.precision == 0 && a.y_out == nullptr && a.M >= min_rows && a.M * 512 < (int64_t)1 << 32 && units_back_to_back(a.wpk) &&
+         fwd_saves(a) >= 0 && a.resid != nullptr && a.scale != nullptr && a.out != a.resid && a.out != a.src[0];
+}
+// ping-pong: every CU gets at least two 128-row tiles (on a one-tile launch the alternation only doubles the tile's latency)
+static bool fwd_pp_ok(const mgn_mlp_fwd_args& a, const Switches& w) {
+  if (w.pp == 0 || (w.pp < 0 && fwd_saves(a) != 0)) return false;
+  return fwd_edge_stream_ok(a, w.pp == 2 ? 1 : 2 * 128 * 256);
+}
+// register-resident weights: from 65 536 rows (every CU gets >= 8 groups of 32 rows: below that the two-slot lag of its second half
+// is not amortised).  Its gathers address Pd / Ps rows with 32-bit byte offsets (row * 512): both sources need a known row count below 2^23.
+static bool fwd_ppr_ok(const mgn_mlp_fwd_args& a, const Switches& w) {
+  if (w.ppr == 0) return false;
+  for (int q = 0; q < 2; ++q)
+    if (a.add_rows[q] <= 0 || a.add_rows[q] * 512 >= (int64_t)1 << 32) return false;
+  return fwd_edge_stream_ok(a, w.ppr == 2 ? 1 : 65536);
+}
+static unsigned ppr_groups(int64_t M) {  // workgroups of a ppr launch: one per group of PPR_R 16-row tiles, 256 at most
+  const int64_t ngroups = ((M + 15) / 16 + PPR_R - 1) / PPR_R;
+  return (ngroups < 256) ? (unsigned)ngroups : 256u;
+}
+
+// Valid for H in {16, 32, 64, 128} and NL in range (check_mlp_common); any other field may still be out of range.
+static MlpRoute route_fwd(const mgn_mlp_fwd_args& a, const Switches& w) {
+  bool ragged = (a.out_w != a.H) || a.nphase > MGN_MAX_PHASES;  // (a phase count out of range is refused by the caller)
+  for (int p = 0; p < a.nphase && p < MGN_MAX_PHASES; ++p) ragged = ragged || (a.kw[p] != a.H);
+  const MlpPlan p = plan_mlp(w, a.M, a.H, a.NL, ragged, false, a.act);
+  MlpRoute r;
+  r.lds_path = p.lds;
+  r.lds_shape = p.lds_shape;
+  r.x6 = fwd_x6(a, w);
+  r.grid = p.grid;
+  r.block = 256;
+  r.lds = p.smem;
+  r.nblocks = 0;
+  if (!p.lds) {  // (ragged: encoders / decoder, guarded generic first / last layer)
+    r.kernel = K_FWD_GEN + generic_row(a.H, ragged, p.mt);
+    return r;
+  }
+  if (!r.x6) {
+    r.kernel = K_FWD_LDS + (p.mt == 2 ? 0 : 1);
+    return r;
+  }
+  // 4 waves per workgroup at every M; 8-wave workgroups, one per CU, are the MGN_NW=8 override (no fused segment sum, no SiLU there)
+  const bool silu = (a.act == MGN_ACT_SILU);
+  const int nw = (w.nw == 8 && a.seg_out == nullptr && !silu) ? 8 : 4;
+  const bool nw6 = (w.nw == 6);
+  const int fp32 = (a.precision >= 1) ? 0 : 1;
+  const int rows = 16 * nw;
+  r.grid = (unsigned)((a.M + rows - 1) / rows);
+  const unsigned cap = (nw == 8) ? 256u : 512u;
+  if (r.grid > cap) r.grid = cap;
+  if (w.grid > 0 && (unsigned)w.grid < r.grid) r.grid = (unsigned)w.grid;
+  r.block = 64 * nw;
+  r.lds = X6_FWD_LDS_BYTES(nw);
+  const int shape = (nw == 4 && !silu) ? fwd_static_shape(a, w) : 0;
+  if (shape == 1 && !nw6 && fwd_ppr_ok(a, w)) {
+    r.kernel = K_FWD_PPR + (a.saveU != nullptr ? 0 : 1) + (w.ppr_xcd ? 0 : 2);
+    r.grid = ppr_groups(a.M);
+    r.block = 512;
+    r.lds = PPR_LDS_BYTES;
+  } else if (shape == 1 && !nw6 && fwd_pp_ok(a, w)) {
+    r.kernel = K_FWD_PP + (a.saveU != nullptr ? 0 : 1);
+    r.grid = (unsigned)((a.M + 127) / 128);
+    if (r.grid > 256u) r.grid = 256u;
+    r.block = 512;
+    r.lds = PP_LDS_BYTES;
+  } else if (shape == 1 && nw6 && a.precision == 0) {
+    r.kernel = K_FWD_NW6;
+    r.grid = (unsigned)((a.M + 95) / 96);
+    if (r.grid > 512u) r.grid = 512u;
+    r.block = 384;
+    r.lds = X6_FWD_LDS_BYTES(6);
+  } else if (shape != 0) {
+    r.kernel = (shape == 1 ? K_FWD_EDGE : shape == 2 ? K_FWD_NODE2 : K_FWD_NODE0) + fp32;
+  } else if (silu) {
+    r.kernel = K_FWD_SILU + fp32;
+  } else if (nw == 8) {
+    r.kernel = fp32 ? K_FWD_NW8 : K_FWD_NW8_BF16;
+  } else {
+    r.kernel = K_FWD_DYN + (1 - fp32);
+  }
+  return r;
+}
+
+static bool bwd_x6(const mgn_mlp_bwd_args& a, const Switches& w) {
+  if (a.wpk[0] == nullptr || w.fp32_mfma) return false;
+  const int G = a.n_front + a.NL - 1 + a.n_din;
+  if (G > 8 || G < 1 || a.n_front < 0 || a.n_front > MGN_MAX_PHASES) return false;
+  if (a.n_front > 0 && a.dOut2 != nullptr) return false;
+  for (int u = 0; u < G; ++u)
+    if (a.wpk[u] == nullptr) return false;
+  if (a.seg_out != nullptr && (a.seg_key == nullptr || a.seg_rowptr == nullptr || a.seg_part == nullptr || a.dZ[0] == nullptr ||
+                               a.n_front > 0 || a.act != MGN_ACT_RELU || a.precision != 0 || a.NL < 2))
+    return false;
+  if (a.act == MGN_ACT_SILU) {
+    if (a.n_front > 0 || (a.n_din == 0 && a.dOut2 != nullptr)) return false;  // see k_mlp_bwd_x6: pd2 carries the z rows
+    for (int l = 1; l < a.NL; ++l)
+      if (a.Zs[l - 1] == nullptr) return false;
+    return true;
+  }
+  for (int l = 1; l < a.NL; ++l)
+    if (a.Ms[l - 1] == nullptr) return false;  // the split-bf16 chain reads ReLU masks as bits
+  return true;
+}
+// The register-resident-weights edge backward chain (mgn_ppr.inc) takes an SbEdge launch when it is fp32-grade, its four units lie
+// back to back, only dscale is asked for as a column sum, every dZ is written as fp32 rows and the outputs alias no input (rows past
+// M are computed as copies of row M - 1 and stored there again), from 65 536 rows.  Its gather of dOut2 uses 32-bit byte offsets
+// (row * 512): dOut2 needs a known row count below 2^23.
+static bool bwd_ppr_ok(const mgn_mlp_bwd_args& a, const Switches& w) {
+  if (w.ppr == 0 || !w.ppr_bwd) return false;
+  const int64_t min_rows = (w.ppr == 2) ? 1 : 65536;
+  if (a.precision != 0 || a.M < min_rows || a.M * 512 >= (int64_t)1 << 32 || a.dscale == nullptr) return false;
+  if (a.dOut2_rows <= 0 || a.dOut2_rows * 512 >= (int64_t)1 << 32 || !units_back_to_back(a.wpk)) return false;
+  for (int l = 0; l < 4; ++l)
+    if (a.db[l] != nullptr || a.dZ[l] == nullptr) return false;
+  if (a.dIn[0] == nullptr || a.Ms[0] == nullptr || a.Ms[1] == nullptr || a.Ms[2] == nullptr) return false;
+  const void* ins[4] = {a.dOut, a.U, a.din_resid[0], a.dOut2};
+  const void* outs[5] = {a.dZ[0], a.dZ[1], a.dZ[2], a.dZ[3], a.dIn[0]};
+  for (const void* o : outs)
+    for (const void* i : ins)
+      if (o == i) return false;
+  return true;
+}
+
+// Valid for H and NL in range, as route_fwd.
+static MlpRoute route_bwd(const mgn_mlp_bwd_args& a, const Switches& w) {
+  const MlpPlan p = plan_bwd(w, a.M, a.H, a.NL, a.out_w, a.n_din, a.act);
+  MlpRoute r;
+  r.lds_path = p.lds;
+  r.lds_shape = p.lds_shape;
+  r.x6 = bwd_x6(a, w);
+  r.grid = p.grid;
+  r.block = 256;
+  r.lds = p.smem;
+  r.nblocks = (int)p.grid;
+  if (!p.lds) {
+    r.kernel = K_BWD_GEN + generic_row(a.H, a.out_w != a.H, p.mt);
+    return r;
+  }
+  if (!r.x6) {
+    r.kernel = K_BWD_LDS + (p.mt == 2 ? 0 : 1);
+    return r;
+  }
+  int nused = (a.scale != nullptr && a.dscale != nullptr) ? 1 : 0;  // column-sum slots the launch keeps in LDS
+  for (int l = 0; l < a.NL; ++l) nused += (a.db[l] != nullptr) ? 1 : 0;
+  r.lds = X6_BWD_LDS_BYTES(nused);
+  const int bf16 = (a.precision >= 1) ? 1 : 0;
+  const bool front = a.n_front > 0;
+  // static-shape instantiation (mgn_x6.inc, SbEdge): the edge chain of a round, matched field by field
+  const bool sb_edge = w.x6_static != 0 && !front && a.seg_out == nullptr && a.act == MGN_ACT_RELU && a.NL == 4 && a.n_din == 1 &&
+                       a.din_resid[0] != nullptr && a.scale != nullptr && a.R != nullptr && a.U != nullptr && a.dOut2 != nullptr &&
+                       a.idx2 != nullptr;
+  if (sb_edge && bwd_ppr_ok(a, w)) {
+    r.kernel = K_BWD_PPR + (w.ppr_xcd ? 0 : 1);
+    r.grid = ppr_groups(a.M);
+    if (r.grid > p.grid) r.grid = p.grid;  // (the column reduction reads p.grid partials: never more workgroups than that)
+    r.block = 512;
+    r.lds = PPB_LDS_BYTES;
+  } else if (sb_edge) {
+    r.kernel = K_BWD_EDGE + bf16;
+  } else if (a.seg_out != nullptr) {
+    r.kernel = K_BWD_SEG;
+  } else if (a.act == MGN_ACT_SILU) {
+    r.kernel = K_BWD_SILU + bf16;
+  } else {
+    r.kernel = (front ? K_BWD_FRONT : K_BWD_DYN) + bf16;
+  }
+  return r;
+}
+
+extern "C" {
+
 static int check_mlp_common(int H, int NL, int out_w, const char* who) {
   if (!(H == 16 || H == 32 || H == 64 || H == 128)) return fail(1, "H must be 16, 32, 64 or 128");
   if (NL < 1 || NL > MGN_MAX_LAYERS) return fail(1, "NL out of range");
@@ -2716,38 +2747,32 @@ static int check_mlp_common(int H, int NL, int out_w, const char* who) {
 int mgn_mlp_fwd(const mgn_mlp_fwd_args* args, void* stream) {
   const mgn_mlp_fwd_args& a = *args;
   if (int rc = check_mlp_common(a.H, a.NL, a.out_w, "mgn_mlp_fwd")) return rc;
+  const Switches w = read_switches();
+  const MlpRoute r = route_fwd(a, w);
   if (a.precision < 0 || a.precision > 2) return fail(1, "mgn_mlp_fwd: precision must be 0 (fp32-grade), 1 (bf16) or 2 (bf16, two-byte saves)");
-  if (a.precision == 2 && (!fwd_x6(a) || !plan_mlp(a.M, a.H, a.NL, fwd_ragged(a), false, a.act).lds || a.act != MGN_ACT_RELU))
+  if (a.precision == 2 && (!r.x6 || !r.lds_path || a.act != MGN_ACT_RELU))
     return fail(1, "mgn_mlp_fwd: precision 2 (two-byte saves) needs the packed split-bf16 path (H = 128, wpk[]) and ReLU");
-  if (a.seg_out != nullptr && !(plan_mlp(a.M, a.H, a.NL, fwd_ragged(a), false).lds && fwd_x6(a)))
+  if (a.seg_out != nullptr && !(r.lds_shape && r.x6))
     return fail(1, "mgn_mlp_fwd: the fused segment sum needs the packed split-bf16 path (and seg_key / seg_rowptr / seg_part, no post-products)");
-  if (a.out_relu && (a.scale != nullptr || a.resid != nullptr || a.wpk[0] != nullptr ||
-                     plan_mlp(a.M, a.H, a.NL, fwd_ragged(a), false).lds))
+  if (a.out_relu && (a.scale != nullptr || a.resid != nullptr || a.wpk[0] != nullptr || r.lds_shape))
     return fail(1, "mgn_mlp_fwd: out_relu is for a plain ragged-input launch (no norm / residual / packed path)");
   if (a.act != MGN_ACT_RELU && a.act != MGN_ACT_SILU && a.act != MGN_ACT_GELU) return fail(1, "mgn_mlp_fwd: act must be MGN_ACT_RELU, _SILU or _GELU");
   if (a.act == MGN_ACT_GELU && (a.wpk[0] != nullptr || a.precision != 0 || a.seg_out != nullptr || a.n_add > 0 || a.n_post > 0 || a.ldw0 > 0))
     return fail(1, "mgn_mlp_fwd: GELU runs on the generic kernels only (no packed weights / gathers / post-products)");
-  if (a.act == MGN_ACT_SILU && plan_mlp(a.M, a.H, a.NL, fwd_ragged(a), false).lds && !fwd_x6(a) && a.NL > 1)
+  if (a.act == MGN_ACT_SILU && r.lds_shape && !r.x6 && a.NL > 1)
     return fail(1, "mgn_mlp_fwd: SiLU is not available on the exact-fp32 LDS generation (pass packed weights)");
-  if (a.precision >= 1 && plan_mlp(a.M, a.H, a.NL, fwd_ragged(a), false, a.act).lds && !fwd_x6(a))
+  if (a.precision >= 1 && r.lds_path && !r.x6)
     return fail(1, "mgn_mlp_fwd: at H = 128 with full widths the bf16 matrix mode needs the packed split-bf16 path (wpk); other shapes run it on the generic kernels");
   if (a.nphase < 1 || a.nphase > MGN_MAX_PHASES) return fail(1, "mgn_mlp_fwd: nphase out of range");
   for (int p = 0; p < a.nphase; ++p)
     if (a.kw[p] < 1 || a.kw[p] > a.H) return fail(1, "mgn_mlp_fwd: phase width out of range");
   if (a.scale != nullptr && a.out_w != a.H) return fail(1, "mgn_mlp_fwd: RMSNorm needs out_w == H");
   if (a.n_add < 0 || a.n_add > 2 || a.n_post < 0 || a.n_post > 2) return fail(1, "mgn_mlp_fwd: n_add / n_post out of range");
-  if ((a.n_add > 0 || a.n_post > 0 || a.ldw0 > 0) && !plan_mlp(a.M, a.H, a.NL, fwd_ragged(a), false).lds)
+  if ((a.n_add > 0 || a.n_post > 0 || a.ldw0 > 0) && !r.lds_shape)
     return fail(1, "mgn_mlp_fwd: ldw0 / n_add / n_post need the H = 128 full-width kernel");
   if (a.M == 0) return 0;
-  hipStream_t s = (hipStream_t)stream;
-  int rc;
-  switch (a.H) {
-    case 128: rc = launch_fwd<8>(a, s); break;
-    case 64: rc = launch_fwd<4>(a, s); break;
-    case 32: rc = launch_fwd<2>(a, s); break;
-    default: rc = launch_fwd<1>(a, s); break;
-  }
-  if (rc) return fail(2, "mgn_mlp_fwd: cannot reserve LDS");
+  if (reserve_lds(r.kernel)) return fail(2, "mgn_mlp_fwd: cannot reserve LDS");
+  launch(r.kernel, dim3(r.grid), r.block, r.lds, (hipStream_t)stream, a);
   return check_launch("mgn_mlp_fwd");
 }
 
@@ -2761,10 +2786,12 @@ size_t mgn_mlp_bwd_workspace_bytes(int64_t M, int H, int NL) {
 int mgn_mlp_bwd(const mgn_mlp_bwd_args* args, void* stream) {
   const mgn_mlp_bwd_args& a = *args;
   if (int rc = check_mlp_common(a.H, a.NL, a.out_w, "mgn_mlp_bwd")) return rc;
+  const Switches w = read_switches();
+  const MlpRoute r = route_bwd(a, w);
   if (a.n_din < 0 || a.n_din > MGN_MAX_PHASES) return fail(1, "mgn_mlp_bwd: n_din out of range");
   if (a.n_din > 1 && a.dZ[0] == nullptr) return fail(1, "mgn_mlp_bwd: n_din > 1 needs dZ[0]");
   if (a.precision < 0 || a.precision > 3) return fail(1, "mgn_mlp_bwd: precision must be 0 (fp32-grade), 1 (bf16), 2 (bf16, two-byte dZ[1..]) or 3 (dZ[0] too)");
-  if (a.precision >= 2 && (!bwd_x6(a) || !plan_mlp(a.M, a.H, a.NL, a.out_w != a.H || a.n_din > 1, true).lds || a.act != MGN_ACT_RELU || a.n_front != 0))
+  if (a.precision >= 2 && (!r.x6 || !r.lds_shape || a.act != MGN_ACT_RELU || a.n_front != 0))
     return fail(1, "mgn_mlp_bwd: precision 2 (two-byte dZ rows) needs the packed split-bf16 path (H = 128, wpk, Ms), ReLU and no front stage");
   if (a.act != MGN_ACT_RELU && a.act != MGN_ACT_SILU && a.act != MGN_ACT_GELU) return fail(1, "mgn_mlp_bwd: act must be MGN_ACT_RELU, _SILU or _GELU");
   if (a.act == MGN_ACT_GELU && (a.wpk[0] != nullptr || a.precision != 0 || a.seg_out != nullptr || a.n_front != 0))
@@ -2774,29 +2801,25 @@ int mgn_mlp_bwd(const mgn_mlp_bwd_args* args, void* stream) {
       if (a.Zs[l - 1] == nullptr) return fail(1, "mgn_mlp_bwd: SiLU / GELU need the saved pre-activations Zs[]");
   }
   if (a.act == MGN_ACT_SILU) {
-    if (plan_mlp(a.M, a.H, a.NL, a.out_w != a.H || a.n_din > 1, true).lds && !bwd_x6(a))
+    if (r.lds_shape && !r.x6)
       return fail(1, "mgn_mlp_bwd: SiLU is not available on the exact-fp32 LDS generation (pass packed weights)");
   }
-  if (a.n_front != 0 && !(plan_mlp(a.M, a.H, a.NL, a.out_w != a.H || a.n_din > 1, true).lds && bwd_x6(a)))
+  if (a.n_front != 0 && !(r.lds_shape && r.x6))
     return fail(1, "mgn_mlp_bwd: the front stage needs the packed split-bf16 path (H = 128, full widths, wpk, Ms, no dOut2)");
-  if (a.precision >= 1 && plan_mlp(a.M, a.H, a.NL, a.out_w != a.H || a.n_din > 1, true, a.act).lds && !bwd_x6(a))
+  if (a.precision >= 1 && r.lds_path && !r.x6)
     return fail(1, "mgn_mlp_bwd: at H = 128 with full widths the bf16 matrix mode needs the packed split-bf16 path (wpk, Ms); other shapes run it on the generic kernels");
-  if (a.seg_out != nullptr && !(plan_mlp(a.M, a.H, a.NL, a.out_w != a.H || a.n_din > 1, true).lds && bwd_x6(a)))
+  if (a.seg_out != nullptr && !(r.lds_shape && r.x6))
     return fail(1, "mgn_mlp_bwd: the fused segment sum of dZ[0] needs the packed split-bf16 path (fp32-grade, ReLU, dZ[0], no front stage)");
   if (a.M == 0) return 0;
   if (a.red_ws_bytes < mgn_mlp_bwd_workspace_bytes(a.M, a.H, a.NL)) return fail(1, "mgn_mlp_bwd: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  int lrc;
-  switch (a.H) {
-    case 128: lrc = launch_bwd<8>(a, s); break;
-    case 64: lrc = launch_bwd<4>(a, s); break;
-    case 32: lrc = launch_bwd<2>(a, s); break;
-    default: lrc = launch_bwd<1>(a, s); break;
-  }
-  if (lrc) return fail(2, "mgn_mlp_bwd: cannot reserve LDS");
+  if (reserve_lds(r.kernel)) return fail(2, "mgn_mlp_bwd: cannot reserve LDS");
+  if (kKernels[r.kernel].sig == SIG_BWD_PPR)
+    launch(r.kernel, dim3(r.grid), r.block, r.lds, s, a, r.nblocks);
+  else
+    launch(r.kernel, dim3(r.grid), r.block, r.lds, s, a);
   if (int rc = check_launch("mgn_mlp_bwd")) return rc;
   // column reductions: db[l], dscale
-  const unsigned grid = plan_mlp(a.M, a.H, a.NL, a.out_w != a.H || a.n_din > 1, true, a.act).grid;
   const int nslot = a.NL + 1;
   ColredOuts outs;
   bool any = false;
@@ -2809,12 +2832,13 @@ int mgn_mlp_bwd(const mgn_mlp_bwd_args* args, void* stream) {
   any |= outs.o[a.NL] != nullptr;
   if (!any || a.defer_reduce) return 0;  // deferred: the caller finishes with mgn_colred_batch
   const int n = nslot * a.H;
-  hipLaunchKernelGGL(k_colred, dim3((n + 31) / 32), dim3(1024), 0, s, (const float*)a.red_ws, (int)grid, nslot, a.H, outs);
+  hipLaunchKernelGGL(k_colred, dim3((n + 31) / 32), dim3(1024), 0, s, (const float*)a.red_ws, r.nblocks, nslot, a.H, outs);
   return check_launch("mgn_mlp_bwd/colred");
 }
 
 int mgn_colred_batch(int n, const mgn_colred_job* jobs, void* stream) {
   if (n < 0) return fail(1, "mgn_colred_batch: bad arguments");
+  const Switches w = read_switches();
   hipStream_t s = (hipStream_t)stream;
   for (int i0 = 0; i0 < n; i0 += CR_MAX) {
     ColredBatch B;
@@ -2825,7 +2849,9 @@ int mgn_colred_batch(int n, const mgn_colred_job* jobs, void* stream) {
       if (q.red_ws == nullptr || q.NL < 1 || q.NL > MGN_MAX_LAYERS) return fail(1, "mgn_colred_batch: bad job");
       ColredJob& J = B.j[i];
       J.ws = (const float*)q.red_ws;
-      J.nblocks = (int)plan_mlp(q.M, q.H, q.NL, q.out_w != q.H || q.n_din > 1, true).grid;
+      // (a job carries no activation: the plan of a ReLU / SiLU launch.  A GELU launch at H = 128 with full widths leaves the
+      //  generic kernels' block count and must not be deferred.)
+      J.nblocks = (int)plan_bwd(w, q.M, q.H, q.NL, q.out_w, q.n_din, MGN_ACT_RELU).grid;
       J.nslot = q.NL + 1;
       J.H = q.H;
       for (int l = 0; l <= MGN_MAX_LAYERS; ++l) J.outs.o[l] = nullptr;
@@ -2842,22 +2868,15 @@ static bool wgrad_job_row64(const mgn_wgrad_job& j) {
   return j.nja <= 4 && j.nkb <= 4 && j.kw <= 64 && (j.kw & 3) == 0 && (j.lda & 3) == 0 && (j.ldb & 3) == 0 &&
          (((uintptr_t)j.A | (uintptr_t)j.B) & 15) == 0;
 }
-static int wgrad_plan(int njobs, const mgn_wgrad_job* jobs, int* wg0, bool lds, int lds_budget = 512) {
+static int wgrad_plan(int njobs, const mgn_wgrad_job* jobs, int* wg0, bool lds, int budget) {
   // A fixed budget of workgroups -- at most what is co-resident (512 = 2 per CU for the LDS
   // kernel; the generic one could hold 1024) -- shared out in proportion to the rows of each job.
   // The total must NEVER exceed the budget: four workgroups too many start a second
   // scheduling round and the kernel takes 1.4x as long (measured).  Floor shares first, the
   // remainder goes to the jobs with the most tiles per workgroup.
-  const int rows = lds ? WG_TILE_ROWS : 16;
   // (generic kernel: 1024 workgroups are co-resident, but half as many leave half the partials to k_wgrad_red -- neutral on the
   //  headline, -3.5 % on the Transformer step whose weight gradients are all small matrices; MGN_WGRAD_GENERIC_BUDGET overrides)
-  int budget = lds ? lds_budget : 512;
-  if (!lds) {
-    if (const char* e = getenv("MGN_WGRAD_GENERIC_BUDGET")) {
-      const int b = atoi(e);
-      if (b >= 64 && b <= 1024) budget = b;
-    }
-  }
+  const int rows = lds ? WG_TILE_ROWS : 16;
   int64_t tiles[MGN_MAX_WGRAD_JOBS], tot = 0;
   int n[MGN_MAX_WGRAD_JOBS];
   for (int j = 0; j < njobs; ++j) {
@@ -2903,9 +2922,88 @@ size_t mgn_wgrad_workspace_bytes(int njobs, const mgn_wgrad_job* jobs) {
   return (size_t)(512 + 1024 + 2 * MGN_MAX_WGRAD_JOBS) * (128 * 128 + 128) * sizeof(float);
 }
 
-static bool wgrad_job_full(const mgn_wgrad_job& j) {
+static bool wgrad_job_full(const mgn_wgrad_job& j, const Switches& w) {
   // (ldb == -128: B holds the forward's two-byte saves, split-bf16 kernel in the bf16 matrix mode only -- checked by mgn_wgrad_p)
-  return j.nja == 8 && j.nkb == 8 && (j.lda == 128 || j.lda == -128) && (j.ldb == 128 || j.ldb == -128) && j.kw == 128 && j.M >= 1 && getenv("MGN_NO_LDS") == nullptr;
+  return j.nja == 8 && j.nkb == 8 && (j.lda == 128 || j.lda == -128) && (j.ldb == 128 || j.ldb == -128) && j.kw == 128 && j.M >= 1 && !w.no_lds;
+}
+
+struct WgradRoute {
+  int kernel, red;  // rows of kKernels: the pass's kernel and the k_wgrad_red that follows it; kernel < 0: no job for this pass
+  unsigned block;
+  size_t lds;       // dynamic LDS bytes of the launch
+  int total;        // workgroups = partial slabs of L.H * L.H + L.H floats in the workspace
+};
+// One of the two launches of mgn_wgrad_p: pass 0 takes the full 128 x 128 jobs (LDS-staged kernels), pass 1 the others.  Decides
+// which jobs, the width, the kernel and the hand-out of the workgroups, and fills L with all of it but `partial`; ws_left is what
+// the pass may use of the workspace.  Returns the text of a refusal, or null.  No HIP call, no global state.
+static const char* route_wgrad(int pass, int njobs, const mgn_wgrad_job* jobs, int precision, size_t ws_left, const Switches& w,
+                               WgradLaunch& L, WgradRoute& r) {
+  r.kernel = -1;
+  L.njobs = 0;
+  int maxb = 1;
+  for (int j = 0; j < njobs; ++j) {
+    if (jobs[j].nja < 1 || jobs[j].nkb < 1 || jobs[j].nja > 8 || jobs[j].nkb > 8) return "mgn_wgrad: block counts out of range";
+    if (wgrad_job_full(jobs[j], w) != (pass == 0)) continue;
+    L.job[L.njobs++] = jobs[j];
+    if (jobs[j].nja > maxb) maxb = jobs[j].nja;
+    if (jobs[j].nkb > maxb) maxb = jobs[j].nkb;
+  }
+  if (L.njobs == 0) return nullptr;
+  int HB = maxb <= 1 ? 1 : maxb <= 2 ? 2 : maxb <= 4 ? 4 : 8;
+  // jobs up to 64 x 64 with 16-byte addressable rows: the row-vector kernel
+  bool row64 = pass == 1 && HB <= 4 && !w.wgrad_no_row64;
+  for (int j = 0; row64 && j < L.njobs; ++j) row64 = wgrad_job_row64(L.job[j]);
+  if (row64) HB = 4;
+  if (!row64 && pass == 1)  // (only k_wgrad_x6<1> and k_wgrad_row64<true> read two-byte rows)
+    for (int j = 0; j < L.njobs; ++j)
+      if (L.job[j].lda < 0 || L.job[j].ldb < 0) return "mgn_wgrad: bf16-row jobs below 128 x 128 need every job of the launch on the row-vector kernel";
+  L.H = 16 * HB;
+  // [r5] fp32-row full jobs: the producer / consumer kernel (one 512-thread workgroup per CU)
+  bool pc = pass == 0 && precision == 0 && !w.fp32_mfma && w.wgrad_pc;
+  for (int j = 0; pc && j < L.njobs; ++j) pc = L.job[j].lda == 128 && L.job[j].ldb == 128;
+  r.total = wgrad_plan(L.njobs, L.job, L.wg0, pass == 0, pass == 1 ? w.wgrad_generic_budget : pc ? 256 : 512);
+  L.interleave = 0;
+  if (row64 && L.njobs >= 2 && L.njobs <= 8 && !w.wgrad_no_interleave) {
+    bool same = true;
+    for (int j = 1; j < L.njobs; ++j) same = same && L.job[j].M == L.job[0].M;
+    const int64_t tiles = (L.job[0].M + 15) / 16;
+    int per = (512 / L.njobs) & ~7;                        // workgroups per job: a multiple of 8, at most the usual budget together
+    while (per > 8 && (int64_t)per * 4 > tiles) per -= 8;  // (at least ~4 tiles per workgroup)
+    if (same && per >= 8 && tiles >= 4 * per) {
+      for (int j = 0; j <= L.njobs; ++j) L.wg0[j] = j * per;
+      L.interleave = per;
+      r.total = L.njobs * per;
+    }
+  }
+  if (ws_left < (size_t)r.total * (L.H * L.H + L.H) * sizeof(float)) return "mgn_wgrad: workspace too small";
+  r.block = 256;
+  r.lds = 0;
+  if (pc) {
+    r.kernel = K_WGRAD_PC;
+    r.block = 512;
+    r.lds = WPC_LDS_BYTES;
+  } else if (pass == 0) {
+    r.kernel = w.fp32_mfma ? K_WGRAD_LDS : K_WGRAD_X6 + (precision == 1 ? 1 : 0);
+    r.lds = 4 * WG_TILE_BYTES;
+  } else if (row64 && precision == 1) {
+    // two-byte operand rows: one pattern per launch (every job's A, every job's B alike)
+    const bool a16 = L.job[0].lda < 0, b16 = L.job[0].ldb < 0;
+    for (int j = 1; j < L.njobs; ++j)
+      if ((L.job[j].lda < 0) != a16 || (L.job[j].ldb < 0) != b16) return "mgn_wgrad: the jobs of a row-vector launch must agree on which operand is bf16 rows";
+    r.kernel = K_WGRAD_ROW64_BF16 + (a16 && b16 ? 0 : a16 ? 1 : b16 ? 2 : 3);
+  } else if (row64 && !w.fp32_mfma && !w.wgrad_row64_exact) {  // [r5] fp32-grade on the split-bf16 matrix path
+    bool full = true;  // every job is 64 x 64 with kw = 64: no lane is masked
+    for (int j = 0; full && j < L.njobs; ++j) full = L.job[j].nja == 4 && L.job[j].kw == 64;
+    r.kernel = K_WGRAD_ROW64X6 + (full ? 0 : 1);
+  } else if (row64) {
+    r.kernel = K_WGRAD_ROW64;
+  } else {
+    r.kernel = K_WGRAD_GEN + (HB == 8 ? 0 : HB == 4 ? 1 : HB == 2 ? 2 : 3);
+  }
+  int max_nwg = 0;
+  for (int j = 0; j < L.njobs; ++j) max_nwg = (L.wg0[j + 1] - L.wg0[j] > max_nwg) ? L.wg0[j + 1] - L.wg0[j] : max_nwg;
+  r.red = K_WGRAD_RED + (max_nwg <= 64 ? 0 : 1);
+  return nullptr;
 }
 
 int mgn_wgrad(int njobs, const mgn_wgrad_job* jobs, void* ws, size_t ws_bytes, void* stream) {
@@ -2915,12 +3013,13 @@ int mgn_wgrad(int njobs, const mgn_wgrad_job* jobs, void* ws, size_t ws_bytes, v
 int mgn_wgrad_p(int njobs, const mgn_wgrad_job* jobs, void* ws, size_t ws_bytes, int precision, void* stream) {
   if (precision != 0 && precision != 1) return fail(1, "mgn_wgrad: precision must be 0 (fp32-grade) or 1 (bf16)");
   if (njobs < 1 || njobs > MGN_MAX_WGRAD_JOBS) return fail(1, "mgn_wgrad: njobs out of range");
+  const Switches w = read_switches();
   for (int j = 0; j < njobs; ++j) {   // two-byte operands: only what k_wgrad_x6<1> reads
     if (jobs[j].lda < 0 || jobs[j].ldb < 0) {
       // full 128 x 128 jobs (k_wgrad_x6<1>) or, [r5], jobs of the row-vector kernel (k_wgrad_row64<true>: up to 64 x 64)
-      const bool r64 = !wgrad_job_full(jobs[j]) && wgrad_job_row64(jobs[j]) && getenv("MGN_WGRAD_NO_ROW64") == nullptr &&
-                       ((((uintptr_t)jobs[j].A | (uintptr_t)jobs[j].B) & 15) == 0);
-      if (precision != 1 || !(wgrad_job_full(jobs[j]) || r64) || getenv("MGN_FP32_MFMA") != nullptr)
+      const bool full = wgrad_job_full(jobs[j], w);
+      const bool r64 = !full && wgrad_job_row64(jobs[j]) && !w.wgrad_no_row64;
+      if (precision != 1 || !(full || r64) || w.fp32_mfma)
         return fail(1, "mgn_wgrad: a negative leading dimension (bf16 rows) needs precision 1 and a full 128 x 128 job with ld = -128 or a job of the row-vector kernel");
     }
   }
@@ -2929,117 +3028,15 @@ int mgn_wgrad_p(int njobs, const mgn_wgrad_job* jobs, void* ws, size_t ws_bytes,
   size_t ws_off = 0;
   for (int pass = 0; pass < 2; ++pass) {
     WgradLaunch L;
-    L.njobs = 0;
-    int maxb = 1;
-    for (int j = 0; j < njobs; ++j) {
-      if (jobs[j].nja < 1 || jobs[j].nkb < 1 || jobs[j].nja > 8 || jobs[j].nkb > 8) return fail(1, "mgn_wgrad: block counts out of range");
-      if (wgrad_job_full(jobs[j]) != (pass == 0)) continue;
-      L.job[L.njobs++] = jobs[j];
-      if (jobs[j].nja > maxb) maxb = jobs[j].nja;
-      if (jobs[j].nkb > maxb) maxb = jobs[j].nkb;
-    }
-    if (L.njobs == 0) continue;
-    int HB = maxb <= 1 ? 1 : maxb <= 2 ? 2 : maxb <= 4 ? 4 : 8;
-    // jobs up to 64 x 64 with 16-byte addressable rows: the row-vector kernel (MGN_WGRAD_NO_ROW64: the generic one, for A/B)
-    bool row64 = pass == 1 && HB <= 4 && getenv("MGN_WGRAD_NO_ROW64") == nullptr;
-    for (int j = 0; row64 && j < L.njobs; ++j) row64 = wgrad_job_row64(L.job[j]);
-    if (row64) HB = 4;
-    if (!row64 && pass == 1)   // (only k_wgrad_x6<1> and k_wgrad_row64<true> read two-byte rows)
-      for (int j = 0; j < L.njobs; ++j)
-        if (L.job[j].lda < 0 || L.job[j].ldb < 0) return fail(1, "mgn_wgrad: bf16-row jobs below 128 x 128 need every job of the launch on the row-vector kernel");
-    L.H = 16 * HB;
-    // [r5] fp32-row full jobs: the producer / consumer kernel (one 512-thread workgroup per CU); MGN_WGRAD_PC=0: k_wgrad_x6<6>
-    bool pc = pass == 0 && precision == 0 && getenv("MGN_FP32_MFMA") == nullptr;
-    if (pc) {
-      const char* e = getenv("MGN_WGRAD_PC");
-      pc = e == nullptr || atoi(e) != 0;
-      for (int j = 0; pc && j < L.njobs; ++j) pc = L.job[j].lda == 128 && L.job[j].ldb == 128;
-    }
-    int total = wgrad_plan(L.njobs, L.job, L.wg0, pass == 0, pc ? 256 : 512);
-    L.interleave = 0;
-    if (row64 && L.njobs >= 2 && L.njobs <= 8 && getenv("MGN_WGRAD_NO_INTERLEAVE") == nullptr) {
-      bool same = true;
-      for (int j = 1; j < L.njobs; ++j) same = same && L.job[j].M == L.job[0].M;
-      const int64_t tiles = (L.job[0].M + 15) / 16;
-      int per = (512 / L.njobs) & ~7;                       // workgroups per job: a multiple of 8, at most the usual budget together
-      while (per > 8 && (int64_t)per * 4 > tiles) per -= 8;   // (at least ~4 tiles per workgroup)
-      if (same && per >= 8 && tiles >= 4 * per) {
-        for (int j = 0; j <= L.njobs; ++j) L.wg0[j] = j * per;
-        L.interleave = per;
-        total = L.njobs * per;
-      }
-    }
-    const size_t need = (size_t)total * (L.H * L.H + L.H) * sizeof(float);
-    if (ws_bytes < ws_off + need) return fail(1, "mgn_wgrad: workspace too small");
+    WgradRoute r;
+    if (const char* refusal = route_wgrad(pass, njobs, jobs, precision, ws_bytes - ws_off, w, L, r)) return fail(1, refusal);  // (ws_off <= ws_bytes: pass 0 fitted)
+    if (r.kernel < 0) continue;
     L.partial = (float*)((char*)ws + ws_off);
-    ws_off += need;
-    if (pc) {
-      static thread_local bool attr_pc_done = false;
-      if (!attr_pc_done) {
-        if (hipFuncSetAttribute((const void*)k_wgrad_pc, hipFuncAttributeMaxDynamicSharedMemorySize, WPC_LDS_BYTES) != hipSuccess)
-          return fail(2, "mgn_wgrad: cannot reserve LDS");
-        attr_pc_done = true;
-      }
-      hipLaunchKernelGGL(k_wgrad_pc, dim3(total), dim3(512), WPC_LDS_BYTES, s, L);
-    } else if (pass == 0) {
-      const size_t smem = 4 * WG_TILE_BYTES;
-      static thread_local bool attr_done = false;
-      if (!attr_done) {
-        if (hipFuncSetAttribute((const void*)k_wgrad_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-          return fail(2, "mgn_wgrad: cannot reserve LDS");
-        attr_done = true;
-      }
-      if (getenv("MGN_FP32_MFMA") == nullptr) {
-        static thread_local bool attr6_done = false;
-        if (!attr6_done) {
-          if (hipFuncSetAttribute((const void*)k_wgrad_x6<6>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess ||
-              hipFuncSetAttribute((const void*)k_wgrad_x6<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-            return fail(2, "mgn_wgrad: cannot reserve LDS");
-          attr6_done = true;
-        }
-        if (precision == 1)
-          hipLaunchKernelGGL(k_wgrad_x6<1>, dim3(total), dim3(256), smem, s, L);
-        else
-          hipLaunchKernelGGL(k_wgrad_x6<6>, dim3(total), dim3(256), smem, s, L);
-      } else {
-        hipLaunchKernelGGL(k_wgrad_lds, dim3(total), dim3(256), smem, s, L);
-      }
-    } else if (row64) {
-      if (precision == 1) {
-        // two-byte operand rows: one pattern per launch (every job's A, every job's B alike)
-        const bool a16 = L.job[0].lda < 0, b16 = L.job[0].ldb < 0;
-        for (int j = 1; j < L.njobs; ++j)
-          if ((L.job[j].lda < 0) != a16 || (L.job[j].ldb < 0) != b16) return fail(1, "mgn_wgrad: the jobs of a row-vector launch must agree on which operand is bf16 rows");
-        if (a16 && b16) hipLaunchKernelGGL((k_wgrad_row64<true, true, true>), dim3(total), dim3(256), 0, s, L);
-        else if (a16) hipLaunchKernelGGL((k_wgrad_row64<true, true, false>), dim3(total), dim3(256), 0, s, L);
-        else if (b16) hipLaunchKernelGGL((k_wgrad_row64<true, false, true>), dim3(total), dim3(256), 0, s, L);
-        else hipLaunchKernelGGL((k_wgrad_row64<true>), dim3(total), dim3(256), 0, s, L);
-      }
-      else if (getenv("MGN_FP32_MFMA") == nullptr && getenv("MGN_WGRAD_ROW64_EXACT") == nullptr) {   // [r5] fp32-grade on the split-bf16 matrix path
-        bool full = true;
-        for (int j = 0; full && j < L.njobs; ++j) full = L.job[j].nja == 4 && L.job[j].kw == 64;
-        if (full)
-          hipLaunchKernelGGL(k_wgrad_row64x6<true>, dim3(total), dim3(256), 0, s, L);
-        else
-          hipLaunchKernelGGL(k_wgrad_row64x6<false>, dim3(total), dim3(256), 0, s, L);
-      }
-      else
-        hipLaunchKernelGGL(k_wgrad_row64<false>, dim3(total), dim3(256), 0, s, L);
-    } else {
-      switch (HB) {
-        case 8: hipLaunchKernelGGL(k_wgrad<8>, dim3(total), dim3(256), 0, s, L); break;
-        case 4: hipLaunchKernelGGL(k_wgrad<4>, dim3(total), dim3(256), 0, s, L); break;
-        case 2: hipLaunchKernelGGL(k_wgrad<2>, dim3(total), dim3(256), 0, s, L); break;
-        default: hipLaunchKernelGGL(k_wgrad<1>, dim3(total), dim3(256), 0, s, L); break;
-      }
-    }
+    ws_off += (size_t)r.total * (L.H * L.H + L.H) * sizeof(float);
+    if (reserve_lds(r.kernel)) return fail(2, "mgn_wgrad: cannot reserve LDS");
+    launch(r.kernel, dim3(r.total), r.block, r.lds, s, L);
     if (int rc = check_launch("mgn_wgrad")) return rc;
-    int max_nwg = 0;
-    for (int j = 0; j < L.njobs; ++j) max_nwg = (L.wg0[j + 1] - L.wg0[j] > max_nwg) ? L.wg0[j + 1] - L.wg0[j] : max_nwg;
-    if (max_nwg <= 64)
-      hipLaunchKernelGGL(k_wgrad_red<4>, dim3((L.H * L.H + L.H + 63) / 64, L.njobs), dim3(64 * 4), 0, s, L);
-    else
-      hipLaunchKernelGGL(k_wgrad_red<16>, dim3((L.H * L.H + L.H + 63) / 64, L.njobs), dim3(64 * 16), 0, s, L);
+    launch(r.red, dim3((L.H * L.H + L.H + 63) / 64, L.njobs), r.red == K_WGRAD_RED ? 64 * 4 : 64 * 16, 0, s, L);
     if (int rc = check_launch("mgn_wgrad/reduce")) return rc;
   }
   return 0;
@@ -3049,25 +3046,13 @@ int mgn_wgrad_p(int njobs, const mgn_wgrad_job* jobs, void* ws, size_t ws_bytes,
 // query): what the 512-workgroup plans assume.  out[0..5] = fwd_x6<6,4>, fwd_x6<1,4>, bwd_x6<6> with one
 // column-sum slot, bwd_x6<6> with five (the round-1 footprint), wgrad_x6<6>, fwd_x6<6,8>.
 int mgn_debug_occupancy(int* out) {
-  int n = 0;
-  if (hipFuncSetAttribute((const void*)k_mlp_fwd_x6<6, 4, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, X6_FWD_LDS_BYTES(4)) != hipSuccess) return 1;
-  if (hipFuncSetAttribute((const void*)k_mlp_fwd_x6<1, 4, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, X6_FWD_LDS_BYTES(4)) != hipSuccess) return 1;
-  if (hipFuncSetAttribute((const void*)k_mlp_fwd_x6<6, 8, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, X6_FWD_LDS_BYTES(8)) != hipSuccess) return 1;
-  if (hipFuncSetAttribute((const void*)k_mlp_bwd_x6<6, false, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, X6_BWD_LDS_BYTES(LDS_MAX_NL + 1)) != hipSuccess) return 1;
-  if (hipFuncSetAttribute((const void*)k_mlp_bwd_x6<1, false, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, X6_BWD_LDS_BYTES(LDS_MAX_NL + 1)) != hipSuccess) return 1;
-  if (hipFuncSetAttribute((const void*)k_wgrad_x6<6>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * WG_TILE_BYTES) != hipSuccess) return 1;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_mlp_fwd_x6<6, 4, 0>, 256, X6_FWD_LDS_BYTES(4)) != hipSuccess) return 2;
-  out[0] = n;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_mlp_fwd_x6<1, 4, 0>, 256, X6_FWD_LDS_BYTES(4)) != hipSuccess) return 2;
-  out[1] = n;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_mlp_bwd_x6<6, false, 0>, 256, X6_BWD_LDS_BYTES(1)) != hipSuccess) return 2;
-  out[2] = n;  // one column-sum slot (dscale only: what the processor launches)
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_mlp_bwd_x6<6, false, 0>, 256, X6_BWD_LDS_BYTES(5)) != hipSuccess) return 2;
-  out[3] = n;  // all five slots (the round-1 footprint)
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_wgrad_x6<6>, 256, 4 * WG_TILE_BYTES) != hipSuccess) return 2;
-  out[4] = n;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_mlp_fwd_x6<6, 8, 0>, 512, X6_FWD_LDS_BYTES(8)) != hipSuccess) return 2;
-  out[5] = n;
+  if (reserve_lds(K_FWD_DYN) || reserve_lds(K_BWD_DYN) || reserve_lds(K_WGRAD_X6)) return 1;
+  // (one column-sum slot: dscale only, what the processor launches; five: all slots)
+  const struct { int k, block; size_t lds; } q[6] = {{K_FWD_DYN, 256, X6_FWD_LDS_BYTES(4)}, {K_FWD_DYN + 1, 256, X6_FWD_LDS_BYTES(4)},
+                                                     {K_BWD_DYN, 256, X6_BWD_LDS_BYTES(1)}, {K_BWD_DYN, 256, X6_BWD_LDS_BYTES(5)},
+                                                     {K_WGRAD_X6, 256, 4 * WG_TILE_BYTES},  {K_FWD_NW8, 512, X6_FWD_LDS_BYTES(8)}};
+  for (int i = 0; i < 6; ++i)
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&out[i], kKernels[q[i].k].fn, q[i].block, q[i].lds) != hipSuccess) return 2;
   return 0;
 }
 

@@ -356,3 +356,27 @@ def test_csrc_preprocessor_conditionals_name_only_allowed_macros():
             assert names and names <= allowed, f"{f}: '{m.group(0).strip()}' names {sorted(names - allowed) or 'no macro'}"
             seen += 1
     assert seen >= 1  # the timeline build is there: the pattern still finds directives
+
+
+def test_mlp_unit_reads_its_environment_switches_in_one_place():
+    """csrc/mgn_kernels.hip and the .inc files it includes read the environment only inside read_switches(), once per entry-point
+    call, and that reader names exactly the unit's fifteen switches (INTEGRATION.md lists them; the route test flips each one)."""
+    import os
+    import re
+
+    switches = {"MGN_NO_LDS", "MGN_MT", "MGN_GRID", "MGN_FP32_MFMA", "MGN_X6_STATIC", "MGN_PP", "MGN_PPR", "MGN_PPR_XCD", "MGN_PPR_BWD", "MGN_NW",
+                "MGN_WGRAD_GENERIC_BUDGET", "MGN_WGRAD_NO_ROW64", "MGN_WGRAD_PC", "MGN_WGRAD_NO_INTERLEAVE", "MGN_WGRAD_ROW64_EXACT"}
+    csrc = os.path.dirname(gp.__path__[0]) + "/graph-physics_amd/csrc"
+    src = open(os.path.join(csrc, "mgn_kernels.hip")).read()
+    included = set(re.findall(r'^#include "(mgn_\w+\.inc)"', src, flags=re.M))
+    assert {"mgn_x6.inc", "mgn_pp.inc", "mgn_ppr.inc", "mgn_fused.inc"} <= included
+    for f in sorted(included):
+        assert "getenv(" not in open(os.path.join(csrc, f)).read(), f
+    m = re.search(r"^static Switches read_switches\(\) \{\n(.*?)^\}\n", src, flags=re.M | re.S)
+    assert m, "read_switches() not found"
+    assert src.count("getenv(") == m.group(1).count("getenv(") >= 1  # every read of the environment is the reader's
+    assert set(re.findall(r'"(MGN_\w+)"', m.group(1))) == switches
+    assert set(re.findall(r'"(MGN_\w+)"', src)) == switches  # and no other code spells a switch as a string
+    for entry in ("mgn_mlp_fwd", "mgn_mlp_bwd", "mgn_colred_batch", "mgn_wgrad_p"):
+        body = src[src.index(f"\nint {entry}("):]
+        assert body[:body.index("\n}\n")].count("read_switches()") == 1, entry

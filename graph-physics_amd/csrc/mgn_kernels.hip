@@ -1996,7 +1996,7 @@ struct TBlocks {
 __global__ void __launch_bounds__(256) k_transpose_blocks(const TBlocks T, int H) {
   __shared__ float tile[32][33];
   const mgn_tblock B = T.b[blockIdx.y];
-  const int tpr = H / 32 > 0 ? H / 32 : 1;
+  const int tpr = (H + 31) / 32;  // tiles per row, rounded up as mgn_transpose_blocks counts them
   const int tj = (blockIdx.x / tpr) * 32, tk = (blockIdx.x % tpr) * 32;
   const int lx = threadIdx.x & 31, ly = threadIdx.x >> 5;  // 32 x 8
 #pragma unroll

@@ -347,6 +347,8 @@ def segsum(src: torch.Tensor, rowptr: torch.Tensor, perm: Optional[torch.Tensor]
     _require_device(src)
     n = rowptr.numel() - 1
     H = src.shape[1]
+    if not src.is_contiguous():   # the kernels take the width as the row pitch
+        raise ValueError("segsum: src must be contiguous rows (a column slice of a wider tensor is not)")
     if out is None:
         out = torch.empty(n, H, dtype=torch.float32, device=src.device)
     call("mgn_segsum", src.device, _ptr(src), _ptr(rowptr), _ptr(perm), _ptr(out), n, H)
@@ -361,6 +363,8 @@ def seg_fix(rowptr: torch.Tensor, part: torch.Tensor, out: torch.Tensor):
 def segsum2(src: torch.Tensor, rowptr0, perm0, out0, rowptr1, perm1, out1):
     """two segment sums of the same source rows in one launch (H = 128)"""
     n = rowptr0.numel() - 1
+    if not src.is_contiguous():
+        raise ValueError("segsum2: src must be contiguous rows (a column slice of a wider tensor is not)")
     name = "mgn_segsum2_b16" if src.dtype == torch.bfloat16 else "mgn_segsum2"   # (two-byte rows: dZ[0] of precision 3)
     call(name, src.device, _ptr(src), _ptr(rowptr0), _ptr(perm0), _ptr(out0), _ptr(rowptr1), _ptr(perm1), _ptr(out1), n, src.shape[1])
 

@@ -810,3 +810,6 @@ extern "C" int mgn_head_axis_attn_bwd(const float* q, const float* k, const floa
   HAX_LAUNCH(k_head_axis_attn_bwd, lds, q, k, v, y, lse, dy, (long)N, d, sqrtf((float)d), dq, dk, dv);
   return check_launch("mgn_head_axis_attn_bwd");
 }
+
+// ------------------------------------------------------------------ packed star attention (training.use_spatial_mtp)
+#include "mgn_starattn.inc"

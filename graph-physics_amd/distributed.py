@@ -547,6 +547,10 @@ def check_partitioned_loss(param) -> None:
     (The physics losses read the nodal gradient of the physical fields, which on a partition needs the fields' halo rows; the
     data-parallel step -- whole meshes per rank -- takes every loss.)"""
     from .parse_parameters import get_loss
+    if ((param or {}).get("training") or {}).get("use_spatial_mtp", False):
+        # (a star's neighbours may be another rank's rows: the branch would need H and H_neigh of the halo)
+        raise NotImplementedError("training.use_spatial_mtp is not built for the partitioned multi-GPU step (distributed.py): a star's "
+                                  "neighbour rows may live on another rank; train such a config data-parallel, or on one device")
     _, names = get_loss(param or {})
     if names != "L2LOSS":
         raise NotImplementedError(f"the partitioned training step supports the L2 loss only; the config's loss section asks for {names} "

@@ -23,8 +23,9 @@ from typing import Any, Dict, List, Optional, Sequence
 import torch
 
 from .mesh import Graph
+from .processors import EncodeProcessDecode
 from .nodetype import NodeType
-from .parse_parameters import get_gradient_method, get_loss, get_model, get_simulator, matrix_precision_from_config
+from .parse_parameters import get_gradient_method, get_loss, get_model, get_simulator, get_spatial_mtp, matrix_precision_from_config
 from .losses import L2Loss, LossGeometry, MultiLoss
 from . import ops as _ops
 from ._launch import call, stream_object
@@ -182,10 +183,15 @@ class Engine:
     def __init__(self, param: Dict[str, Any], device: torch.device, learning_rate: float = 1e-4,
                  num_steps: int = 1000, warmup: int = 100, grad_clip: float = 1.0, loss_masks: Optional[Sequence[int]] = None,
                  use_previous_data: bool = False, previous_data_start: Optional[int] = None,
-                 previous_data_end: Optional[int] = None):
+                 previous_data_end: Optional[int] = None, seed: int = 0):
         """``loss_masks`` (the LightningModule's ``masks``), ``use_previous_data``, ``previous_data_start`` and
-        ``previous_data_end`` are the LightningModule's arguments of the same names (lightning_module.py:48-51)."""
+        ``previous_data_end`` are the LightningModule's arguments of the same names (lightning_module.py:48-51).  ``seed`` keys the
+        Engine's own random draws (the centres of ``training.use_spatial_mtp``)."""
         self.param, self.device = param, device
+        self.mtp = get_spatial_mtp(param)   # the spatial-MTP settings, None when training.use_spatial_mtp is off (validated here)
+        if self.mtp is not None and matrix_precision_from_config(param) == "bf16":
+            raise NotImplementedError("training.use_spatial_mtp with training.enable_vram_optimizations: the spatial-MTP branch runs in "
+                                      "fp32 only (the bf16 matrix mode is not built for it)")
         _ops.set_matrix_precision(matrix_precision_from_config(param))  # bf16-mixed <=> enable_vram_optimizations
         self.model = get_model(param)
         self.sim = get_simulator(param, self.model, device)
@@ -206,6 +212,12 @@ class Engine:
         #: ``train_<name>``: the WEIGHTED terms); None for a single loss
         self.last_losses = None
         self.learning_rate, self.num_steps, self.warmup, self.grad_clip = learning_rate, num_steps, warmup, grad_clip
+        #: the auxiliary branch of training.use_spatial_mtp (lightning_module.py:133-268), None when the key is off
+        self.spatial_mtp = None
+        self.last_mtp_stats = None   # device scalars of the last step: the module's stats plus sp_mtp/aux_loss
+        self._mtp_hooks, self._mtp_H, self._mtp_H_neigh = (), None, None
+        if self.mtp is not None:
+            self._setup_spatial_mtp(seed)
         self.opt = self._make_optimizer(learning_rate, capturable=False)
         self.step_count = 0
         self.grad_sync = None  # set by distributed.DataParallel: callable(params) all-reducing .grad
@@ -216,7 +228,7 @@ class Engine:
         (lightning_module.py:494-511); the fused multi-tensor implementation when the device
         supports it (one kernel instead of ~15 foreach launches over 296 tensors)."""
         kw = dict(lr=lr, weight_decay=0.0001, betas=(0.9, 0.95))
-        params = list(self.sim.parameters())
+        params = self._train_params()
         import os as _os
         if params and params[0].is_cuda and all(p.dtype == torch.float32 for p in params) and _os.environ.get("MGN_TORCH_ADAMW") is None:
             if getattr(self, "opt", None) is not None and isinstance(self.opt, FusedClipAdamW):
@@ -229,6 +241,100 @@ class Engine:
             except (RuntimeError, ValueError, TypeError):
                 pass
         return torch.optim.AdamW(params, capturable=capturable, **kw) if capturable else torch.optim.AdamW(params, **kw)
+
+    def _train_params(self) -> List[torch.nn.Parameter]:
+        """what the optimiser steps and the clip takes ONE norm over: the simulator's parameters, then the spatial-MTP module's
+        (the reference registers it as a submodule of the LightningModule: clipped and stepped together)"""
+        params = list(self.sim.parameters())
+        if self.spatial_mtp is not None:
+            params += list(self.spatial_mtp.parameters())
+        return params
+
+    # ---------------------------------------------------------------- training.use_spatial_mtp (lightning_module.py:133-268)
+    def _setup_spatial_mtp(self, seed: int):
+        """``LightningModule._setup_spatial_mtp``: the module sized by the decoder's first Linear, a forward pre-hook on the decoder
+        (its input = H) and a forward hook on the node encoder (its output = H_neigh)"""
+        from .spatial_mtp import SpatialMTP1Hop
+        out_head, node_encoder = getattr(self.model, "decode_module", None), getattr(self.model, "nodes_encoder", None)
+        if not isinstance(out_head, torch.nn.Module):
+            raise ValueError("Spatial MTP requires a processor with an output head nn.Module (expected 'decode_module').")
+        if not isinstance(node_encoder, torch.nn.Module):
+            raise ValueError("Spatial MTP requires a processor with an encoder nn.Module (expected 'nodes_encoder').")
+        first = next((m for m in out_head.modules() if isinstance(m, torch.nn.Linear)), None)
+        if first is None:
+            raise ValueError("Unable to infer hidden size for Spatial MTP (no Linear layer in decode module).")
+        cfg = self.mtp
+        self.spatial_mtp = SpatialMTP1Hop(d_model=first.in_features, num_heads=cfg["spatial_mtp_num_heads"],
+                                          num_layers=cfg["spatial_mtp_num_layers"], assume_undirected=cfg["spatial_mtp_assume_undirected"],
+                                          max_neighbors=cfg["spatial_mtp_max_neighbors"]).to(self.device)
+        self.spatial_mtp.seed = int(seed)
+        self._mtp_head = out_head
+        self._mtp_generator = torch.Generator(device=self.device)
+        self._mtp_generator.manual_seed(int(seed))
+
+        def capture_head_input(module, inputs):
+            hidden = inputs[0]
+            self._mtp_H = hidden.reshape(-1, hidden.size(-1)) if hidden.dim() > 2 else hidden
+
+        def capture_nodeenc_output(module, inputs, outputs):
+            self._mtp_H_neigh = outputs.reshape(-1, outputs.size(-1)) if outputs.dim() > 2 else outputs
+
+        self._mtp_hooks = (out_head.register_forward_pre_hook(capture_head_input), node_encoder.register_forward_hook(capture_nodeenc_output))
+
+    def remove_spatial_mtp_hooks(self):
+        for h in self._mtp_hooks:
+            h.remove()
+        self._mtp_hooks = ()
+
+    def _mtp_loss(self, batch: Graph, target: torch.Tensor, centers: Optional[torch.Tensor]):
+        """``_compute_spatial_mtp_loss`` (lightning_module.py:240-268): (aux loss, stats) or (None, {}).  A model that renumbers the
+        mesh for locality hands its encoder and decoder rows in ITS numbering, and each model has its own rule for when
+        (``ops.get_topology`` for EncodeProcessDecode, ``transformer.get_attn_topology`` for EncodeTransformDecode; the temporal
+        block of the former brings the rows back before the decoder).  So every forward records the rank its two hooked modules
+        saw (``model.last_node_rank``), and the captured tensors are brought back to the caller's numbering with exactly those:
+        centres, adjacency and target then all speak the batch's numbering."""
+        H, Hn = self._mtp_H, self._mtp_H_neigh
+        edge_index = getattr(batch, "edge_index", None)
+        if H is None or edge_index is None or target is None or H.size(0) == 0:
+            return None, {}
+        N = int(H.size(0))
+        ranks = getattr(self.model, "last_node_rank", None) or {}
+        if ranks.get("decode_module") is not None:
+            H = H.index_select(0, ranks["decode_module"])
+        if Hn is not None and ranks.get("nodes_encoder") is not None:
+            Hn = Hn.index_select(0, ranks["nodes_encoder"])
+        topo = None
+        if H.is_cuda and isinstance(self.model, EncodeProcessDecode) and self.spatial_mtp.assume_undirected:
+            # the edge topology the model's forward just used (cached per edge_index) already holds the source-grouped CSR; a
+            # renumbered one is in the engine's numbering, and other models build no such topology: the module then groups the
+            # caller's edge_index itself, once per edge_index
+            topo = getattr(batch, "mgn_topology", None)
+            if topo is None:
+                topo = _ops.get_topology(edge_index, N, pos=getattr(batch, "pos", None), renumber=True)
+            if topo.node_order is not None:
+                topo = None
+        if centers is None:
+            B = min(N, self.mtp["spatial_mtp_centers_per_step"])
+            centers = torch.randperm(N, device=H.device, generator=self._mtp_generator)[:B]
+        return self.spatial_mtp(H=H, edge_index=edge_index, centers=centers, out_head=self._mtp_head, target=target, H_neigh=Hn,
+                                topology=topo, step=self.step_count)
+
+    def state_dict(self) -> Dict[str, torch.Tensor]:
+        """the simulator's weights under their own keys plus, with training.use_spatial_mtp, the module's under ``spatial_mtp.`` --
+        where a checkpoint of the reference's LightningModule keeps them"""
+        sd = dict(self.sim.state_dict())
+        if self.spatial_mtp is not None:
+            sd.update({"spatial_mtp." + k: v for k, v in self.spatial_mtp.state_dict().items()})
+        return sd
+
+    def load_state_dict(self, state: Dict[str, torch.Tensor], strict: bool = True):
+        mtp = {k[len("spatial_mtp."):]: v for k, v in state.items() if k.startswith("spatial_mtp.")}
+        rest = {k: v for k, v in state.items() if not k.startswith("spatial_mtp.")}
+        if self.spatial_mtp is not None:
+            self.spatial_mtp.load_state_dict(mtp, strict=strict)
+        elif mtp and strict:
+            raise RuntimeError("load_state_dict: the state holds spatial_mtp.* weights, this Engine was built without training.use_spatial_mtp")
+        return self.sim.load_state_dict(rest, strict=strict)
 
     def _loss(self, batch: Graph, net_out: torch.Tensor, target: torch.Tensor, node_type: torch.Tensor) -> torch.Tensor:
         """the training step's loss (lightning_module.py:278-312)"""
@@ -255,7 +361,9 @@ class Engine:
         self.last_losses = [t.detach() for t in terms]
         return total
 
-    def train_step(self, batch: Graph) -> torch.Tensor:
+    def train_step(self, batch: Graph, mtp_centers: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """one optimiser step; ``mtp_centers`` (tests): the centre nodes of the spatial-MTP branch, in the batch's numbering, instead
+        of the Engine's own draw"""
         self.sim.train()
         lr_now = self.learning_rate * lr_factor(self.step_count, self.warmup, self.num_steps)
         fused = isinstance(self.opt, FusedClipAdamW)
@@ -265,17 +373,25 @@ class Engine:
             for g in self.opt.param_groups:
                 g["lr"] = lr_now
         node_type = batch.x[:, self.sim.node_type_index]
+        if self.spatial_mtp is not None:
+            self._mtp_H = self._mtp_H_neigh = None
         net_out, target, _ = self.sim(batch)
         loss = self._loss(batch, net_out, target, node_type)
+        if self.spatial_mtp is not None:   # lightning_module.py:321-340
+            aux, stats = self._mtp_loss(batch, target, mtp_centers)
+            if aux is not None:
+                loss = loss + self.mtp["spatial_mtp_alpha"] * aux
+                self.last_mtp_stats = {"sp_mtp/aux_loss": aux.detach(), **{k: v.detach() for k, v in stats.items()}}
+            self._mtp_H = self._mtp_H_neigh = None
         self.opt.zero_grad(set_to_none=True)
         loss.backward()
         if self.grad_sync is not None:
-            self.grad_sync(self.sim.parameters())
+            self.grad_sync(self._train_params())
         if fused:  # clip + AdamW in one engine call
             self.opt.step()
             self.last_grad_norm = self.opt.norm_t
         else:
-            self.last_grad_norm = torch.nn.utils.clip_grad_norm_(self.sim.parameters(), self.grad_clip)
+            self.last_grad_norm = torch.nn.utils.clip_grad_norm_(self._train_params(), self.grad_clip)
             self.opt.step()
         self.step_count += 1
         return loss.detach()
@@ -295,6 +411,9 @@ class Engine:
         per-term scalars, refreshed by every replay.
         """
         dev = self.device
+        if self.spatial_mtp is not None:
+            raise NotImplementedError("capture_train_step with training.use_spatial_mtp: the centres, and with them the packed row count, "
+                                      "change every step, so the step has no fixed shape to capture; use train_step")
         assert self.grad_sync is None, "graph capture of the multi-GPU step is not supported yet"
         # >= 1 eager step first: the optimiser creates its state lazily, and state created under
         # capture would be re-zeroed by every replay

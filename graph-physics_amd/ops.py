@@ -179,6 +179,7 @@ class Topology:
         self._error = None   # sticky: a topology whose build reported stray indices raises on EVERY resolve / use
         self._uses = 0
         self.hub_dst = self.hub_src = None
+        self._nbr_src = None     # neighbours_by_source(), built on first use
         if lazy:
             flags = torch.zeros(4, **i32)
             call("mgn_topology_build_async", dev, ei[0].data_ptr(), ei[1].data_ptr(), E, N, _ptr(self.rowptr_dst), _ptr(self.perm_dst),
@@ -207,6 +208,13 @@ class Topology:
         # still deterministic, no atomics).
         self.hub_dst = _chunk_csr(self.rowptr_dst) if din > HUB_CHUNK else None
         self.hub_src = _chunk_csr(self.rowptr_src) if dout > HUB_CHUNK else None
+
+    def neighbours_by_source(self) -> torch.Tensor:
+        """int32 [E]: the destination of every edge, grouped by source -- with ``rowptr_src`` the CSR of each node's out-neighbours
+        (in this topology's numbering; duplicates and self loops as given).  Built once, kept with the topology."""
+        if self._nbr_src is None:
+            self._nbr_src = self.dst_s.index_select(0, self.perm_src.long())
+        return self._nbr_src
 
     @property
     def resolved(self) -> bool:

@@ -212,6 +212,37 @@ def matrix_precision_from_config(param: Dict[str, Any]) -> str:
     return "bf16" if param.get("training", {}).get("enable_vram_optimizations", False) else "fp32"
 
 
+#: the spatial-MTP keys of the ``training`` section and their defaults (training/lightning_module.py:133-149)
+SPATIAL_MTP_DEFAULTS = {"spatial_mtp_alpha": 0.20, "spatial_mtp_centers_per_step": 256, "spatial_mtp_num_heads": 4,
+                        "spatial_mtp_num_layers": 1, "spatial_mtp_assume_undirected": True, "spatial_mtp_max_neighbors": None}
+
+
+def get_spatial_mtp(param: Dict[str, Any]) -> Optional[Dict[str, Any]]:
+    """The spatial-MTP settings of the ``training`` section (``SPATIAL_MTP_DEFAULTS``), or None when ``training.use_spatial_mtp`` is
+    false or absent.  Values the reference would fail on inside its first step, or that the HIP kernels do not cover, raise a
+    ``ValueError`` that names the key."""
+    training = param.get("training", {}) or {}
+    if not training.get("use_spatial_mtp", False):
+        return None
+    out = {k: training.get(k, v) for k, v in SPATIAL_MTP_DEFAULTS.items()}
+    for k in ("spatial_mtp_centers_per_step", "spatial_mtp_num_heads", "spatial_mtp_num_layers"):
+        if isinstance(out[k], bool) or not isinstance(out[k], int) or out[k] < 1:
+            raise ValueError(f"training.{k}: a positive integer, got {out[k]!r}")
+    k = "spatial_mtp_max_neighbors"
+    if out[k] is not None and (isinstance(out[k], bool) or not isinstance(out[k], int) or out[k] < 1):
+        raise ValueError(f"training.{k}: None or a positive integer, got {out[k]!r}")
+    hidden = param.get("model", {}).get("hidden_size")
+    if hidden not in (16, 32, 64, 128):
+        raise ValueError(f"model.hidden_size: training.use_spatial_mtp runs on the dense HIP kernels, which take 16, 32, 64 or 128 "
+                         f"columns, got {hidden!r}")
+    heads = out["spatial_mtp_num_heads"]
+    if hidden % heads != 0 or heads not in (1, 2, 4, 8, 16):
+        raise ValueError(f"training.spatial_mtp_num_heads: {heads} heads must divide model.hidden_size={hidden} and be one of 1, 2, 4, 8, 16")
+    out["spatial_mtp_alpha"] = float(out["spatial_mtp_alpha"])
+    out["spatial_mtp_assume_undirected"] = bool(out["spatial_mtp_assume_undirected"])
+    return out
+
+
 def cylinder_config(message_passing_num: int = 15, hidden_size: int = 128) -> Dict[str, Any]:
     """training_config/cylinder.json with the two benchmark overrides
     (message_passing_num 5->15, hidden_size 32->128; SURVEY.md TL;DR item 1)."""

@@ -70,6 +70,9 @@ class EncodeProcessDecode(nn.Module):
             x = self.nodes_encoder(x_in)
             # encode edges directly in the engine's dst-sorted order (F_e floats per edge to permute)
             e = self.edges_encoder(graph.edge_attr[perm])
+        # the numbering of the rows the two hooked modules see (old -> new rank, None: the caller's): harness.Engine's spatial-MTP
+        # hooks capture the encoder's output and the decoder's input and bring them back to the caller's numbering with these
+        self.last_node_rank = {"nodes_encoder": rank, "decode_module": rank}
         blocks = list(self.processor_list)
         pos = getattr(graph, "pos", None) if self.use_rope else None
         phi = getattr(graph, "phi", None) if self.use_gate else None
@@ -101,6 +104,7 @@ class EncodeProcessDecode(nn.Module):
                 if rank is not None:  # the attention topology is in the caller's numbering
                     x, prev_x, rank = x.index_select(0, rank), prev_x.index_select(0, rank), None
                 x = self.temporal_block(prev_x, x, get_attn_topology(edge_index, n))
+        self.last_node_rank["decode_module"] = rank   # (None where the temporal block already brought the rows back)
         out = x if self.only_processor else self.decode_module(x)
         if rank is not None:  # back to the caller's numbering (the decoder is row-wise: permute its narrow output)
             out = out.index_select(0, rank)

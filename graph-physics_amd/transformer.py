@@ -528,6 +528,8 @@ class EncodeTransformDecode(nn.Module):
         x_in = graph.x if order is None else graph.x.index_select(0, order)
         if order is not None and pos is not None:
             pos = pos.index_select(0, order)
+        # the numbering of the rows the two hooked modules see (as EncodeProcessDecode.forward records it: harness.Engine's spatial MTP)
+        self.last_node_rank = {"nodes_encoder": rank, "decode_module": rank}
         x = x_in if self.only_processor else self.nodes_encoder(x_in)
         if pyg:   # processors.py:372-377: x = block(x, edge_index); the temporal block is handed adj = None (no DGL: no adjacency)
             prev_x = last_x = x

@@ -9,6 +9,8 @@ from .simulator import Simulator  # noqa: F401
 from .parse_parameters import get_model, get_simulator, cylinder_config, plate_config, matrix_precision_from_config  # noqa: F401
 from .parse_parameters import get_loss, get_gradient_method, get_preprocessing, get_spatial_mtp  # noqa: F401
 from .spatial_mtp import SpatialMTP1Hop, star_attention  # noqa: F401
+from .transolver import TransolverProcessor  # noqa: F401
+from .parse_parameters import get_transolver  # noqa: F401
 from .losses import (LossType, MultiLoss, L2Loss, CosineLoss, L1SmoothLoss, GradientL2Loss, ConvectionL2Loss, DivergenceL2Loss,  # noqa: F401
                      DivergenceL1Loss, DivergenceL1SmoothLoss, LossGeometry, compute_gradient)
 from .ops import set_matrix_precision, get_matrix_precision, set_node_renumbering, get_node_renumbering  # noqa: F401

@@ -19,10 +19,12 @@ SOURCES = [os.path.join(_CSRC, "mgn_kernels.hip"), os.path.join(_CSRC, "mgn_prep
            os.path.join(_CSRC, "mgn_subgraph.hip"), os.path.join(_CSRC, "mgn_randedge.hip"), os.path.join(_CSRC, "mgn_knn.hip")]
 DEPS = [os.path.join(_CSRC, "mgn_x6.inc"), os.path.join(_CSRC, "mgn_fused.inc"), os.path.join(_CSRC, "mgn_pp.inc"), os.path.join(_CSRC, "mgn_ppr.inc"),
         os.path.join(_CSRC, "mgn_philox.inc"), os.path.join(_CSRC, "mgn_host.inc"), os.path.join(_CSRC, "mgn_graphprim.inc"),
-        os.path.join(_CSRC, "mgn_rollout.inc"), os.path.join(_CSRC, "mgn_starattn.inc")]  # included by the sources
+        os.path.join(_CSRC, "mgn_rollout.inc"), os.path.join(_CSRC, "mgn_starattn.inc"),
+        os.path.join(_CSRC, "mgn_slice.inc")]  # included by the sources
 HEADER = os.path.join(_REPO, "include", "mgn_hip.h")
 EXT_HEADER = os.path.join(_REPO, "include", "mgn_hip_ext.h")  # entry points added after ABI 136 (EXT_SYMBOLS)
 MTP_HEADER = os.path.join(_REPO, "include", "mgn_hip_mtp.h")  # the spatial-MTP branch (MTP_SYMBOLS)
+SLICE_HEADER = os.path.join(_REPO, "include", "mgn_hip_slice.h")  # the Transolver slice attention (SLICE_SYMBOLS)
 # No packed-fp32 VALU (v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32) in device code: beside a SIMD partner that streams MFMAs
 # one of them takes ~70 cycles instead of ~6 (tools/coissue_probe.hip; plain VALU: 8), and hipcc forms them everywhere --
 # the SLP vectorizer out of scalar code, the legalizer out of float4 arithmetic (csrc/Makefile carries the same flags).
@@ -354,9 +356,26 @@ MTP_SYMBOLS = {
     "mgn_star_attn_bwd": (C.c_int, [C.c_void_p] * 5 + [C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "mgn_star_loss": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
+#: every symbol include/mgn_hip_slice.h declares (the Transolver processor's physics attention: slice weights, the reductions over
+#: the nodes, the broadcast back and the per-row backward; scalar and pointer arguments only), name -> (restype, argtypes); all of
+#: them are defined under csrc/mgn_attn.hip (csrc/mgn_slice.inc) and report through mgn_attn_last_error
+SLICE_SYMBOLS = {
+    "mgn_slice_pass_rows": (C.c_int64, [C.c_int, C.c_int]),
+    "mgn_slice_uniforms": (C.c_int, [C.c_uint64, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "mgn_slice_weights_fwd": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 8 + [C.c_uint64, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int,
+                                        C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mgn_slice_aggregate_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int, C.c_int]),
+    "mgn_slice_aggregate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_size_t, C.c_void_p]),
+    "mgn_slice_expand": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
+    "mgn_slice_rows_bwd_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
+    "mgn_slice_rows_bwd": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64] + [C.c_void_p] * 8 + [C.c_uint64, C.c_void_p, C.c_int,
+                                     C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64] + [C.c_void_p] * 7 + [C.c_size_t, C.c_void_p]),
+}
 _UNIT_OF = {name: unit for unit, group in UNITS.items() for name in group}
 _UNIT_OF.update({name: "prep" for name in EXT_SYMBOLS})
 _UNIT_OF.update({name: "attn" for name in MTP_SYMBOLS})
+_UNIT_OF.update({name: "attn" for name in SLICE_SYMBOLS})
 
 _lib = None
 _lock = threading.Lock()
@@ -383,7 +402,7 @@ def source_hash() -> str:
     import hashlib
 
     h = hashlib.sha256()
-    for f in SOURCES + DEPS + [HEADER, EXT_HEADER, MTP_HEADER]:
+    for f in SOURCES + DEPS + [HEADER, EXT_HEADER, MTP_HEADER, SLICE_HEADER]:
         with open(f, "rb") as fh:
             h.update(os.path.basename(f).encode() + b"\0" + fh.read() + b"\0")
     h.update(" ".join(DEVICE_FLAGS).encode())  # a library built with other code-generation flags is stale too
@@ -456,7 +475,7 @@ def lib():
                 L = C.CDLL(LIB_PATH)
             except OSError as e:
                 raise RuntimeError(f"cannot load {LIB_PATH}: {e}") from e
-            for name, (res, args) in list(SYMBOLS.items()) + list(EXT_SYMBOLS.items()) + list(MTP_SYMBOLS.items()):
+            for name, (res, args) in list(SYMBOLS.items()) + list(EXT_SYMBOLS.items()) + list(MTP_SYMBOLS.items()) + list(SLICE_SYMBOLS.items()):
                 fn = getattr(L, name)
                 fn.restype = res
                 fn.argtypes = args

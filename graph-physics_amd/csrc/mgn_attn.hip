@@ -813,3 +813,6 @@ extern "C" int mgn_head_axis_attn_bwd(const float* q, const float* k, const floa
 
 // ------------------------------------------------------------------ packed star attention (training.use_spatial_mtp)
 #include "mgn_starattn.inc"
+
+// ------------------------------------------------------------------ physics slice attention (model.type "transolver")
+#include "mgn_slice.inc"

@@ -547,6 +547,10 @@ def check_partitioned_loss(param) -> None:
     (The physics losses read the nodal gradient of the physical fields, which on a partition needs the fields' halo rows; the
     data-parallel step -- whole meshes per rank -- takes every loss.)"""
     from .parse_parameters import get_loss
+    if ((param or {}).get("model") or {}).get("type", "") == "transolver":
+        # (the slice reductions run over ALL nodes: slice_norm and slice_token would need an all-reduce across the parts)
+        raise NotImplementedError("model.type 'transolver' is not built for the partitioned multi-GPU step (distributed.py): its slice "
+                                  "tokens are sums over all nodes of the mesh; train such a config data-parallel, or on one device")
     if ((param or {}).get("training") or {}).get("use_spatial_mtp", False):
         # (a star's neighbours may be another rank's rows: the branch would need H and H_neigh of the halo)
         raise NotImplementedError("training.use_spatial_mtp is not built for the partitioned multi-GPU step (distributed.py): a star's "

@@ -25,7 +25,8 @@ import torch
 from .mesh import Graph
 from .processors import EncodeProcessDecode
 from .nodetype import NodeType
-from .parse_parameters import get_gradient_method, get_loss, get_model, get_simulator, get_spatial_mtp, matrix_precision_from_config
+from .parse_parameters import (get_gradient_method, get_loss, get_model, get_simulator, get_spatial_mtp, get_transolver,
+                               matrix_precision_from_config)
 from .losses import L2Loss, LossGeometry, MultiLoss
 from . import ops as _ops
 from ._launch import call, stream_object
@@ -192,8 +193,19 @@ class Engine:
         if self.mtp is not None and matrix_precision_from_config(param) == "bf16":
             raise NotImplementedError("training.use_spatial_mtp with training.enable_vram_optimizations: the spatial-MTP branch runs in "
                                       "fp32 only (the bf16 matrix mode is not built for it)")
+        #: model.type "transolver": built by its own factory (get_model still refuses the type, see get_transolver)
+        self.is_transolver = (param.get("model", {}) or {}).get("type", "") == "transolver"
+        if self.is_transolver:
+            if matrix_precision_from_config(param) == "bf16":
+                raise NotImplementedError("model.type 'transolver' with training.enable_vram_optimizations: the slice attention runs in fp32 "
+                                          "only (the bf16 matrix mode is not built for it)")
+            if self.mtp is not None:
+                raise NotImplementedError("model.type 'transolver' with training.use_spatial_mtp: the Transolver processor has no "
+                                          "nodes_encoder / decode_module for the branch to hook")
         _ops.set_matrix_precision(matrix_precision_from_config(param))  # bf16-mixed <=> enable_vram_optimizations
-        self.model = get_model(param)
+        self.model = get_transolver(param) if self.is_transolver else get_model(param)
+        if self.is_transolver:
+            self.model.noise_seed = int(seed)   # keys the Gumbel noise stream of the slice attention
         self.sim = get_simulator(param, self.model, device)
         # the config's "loss" section (lightning_module.py:86-96); without one: the masked L2, on the code path it always took
         self.loss, self.loss_name = get_loss(param)
@@ -411,6 +423,9 @@ class Engine:
         per-term scalars, refreshed by every replay.
         """
         dev = self.device
+        if self.is_transolver:
+            raise NotImplementedError("capture_train_step with model.type 'transolver' is not verified (the token part between the slice "
+                                      "launches is differentiated by torch autograd inside the backward); use train_step")
         if self.spatial_mtp is not None:
             raise NotImplementedError("capture_train_step with training.use_spatial_mtp: the centres, and with them the packed row count, "
                                       "change every step, so the step has no fixed shape to capture; use train_step")

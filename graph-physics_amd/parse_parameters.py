@@ -144,6 +144,40 @@ def get_model(param: Dict[str, Any], only_processor: bool = False):
     raise ValueError(f"Model type '{model_type}' not supported.")
 
 
+def get_transolver(param: Dict[str, Any]):
+    """The ``TransolverProcessor`` of a ``model.type: "transolver"`` config, with the reference's keys and defaults
+    (training/parse_parameters.py:95-160): ``message_passing_num``, ``hidden_size``, ``num_heads``, ``output_size``, ``dropout`` 0.0,
+    ``mlp_ratio`` 1, ``slice_num`` 32, ``ref`` 8, ``unified_pos``, ``use_rope_embeddings``, ``rope_pos_dimension`` 3, ``rope_base`` 10000,
+    ``use_gated_attention`` and ``training.use_temporal_block``.
+
+    ``get_model`` deliberately STILL refuses this type with its ``NotImplementedError`` (a test pins that refusal, message included):
+    the model is reached through this factory and through ``Engine``, which calls it for this type.  A later change flips
+    ``get_model`` and that test together."""
+    from .transolver import TransolverProcessor
+
+    model = param.get("model", {})
+    if model.get("type", "") != "transolver":
+        raise ValueError(f"get_transolver: model.type is {model.get('type', '')!r}, not 'transolver'")
+    training = param.get("training", {}) or {}
+    return TransolverProcessor(
+        message_passing_num=param["model"]["message_passing_num"],
+        node_input_size=param["model"]["node_input_size"] + NodeType.SIZE,
+        output_size=param["model"]["output_size"],
+        hidden_size=param["model"]["hidden_size"],
+        num_heads=param["model"]["num_heads"],
+        dropout=model.get("dropout", 0.0),
+        mlp_ratio=model.get("mlp_ratio", 1),
+        slice_num=model.get("slice_num", 32),
+        ref=model.get("ref", 8),
+        unified_pos=model.get("unified_pos", False),
+        use_rope_embeddings=model.get("use_rope_embeddings", False),
+        use_gated_attention=model.get("use_gated_attention", False),
+        rope_pos_dimension=model.get("rope_pos_dimension", 3),
+        rope_base=model.get("rope_base", 10000.0),
+        use_temporal_block=training.get("use_temporal_block", False),
+    )
+
+
 def get_simulator(param: Dict[str, Any], model, device: torch.device) -> Simulator:
     return Simulator(
         node_input_size=param["model"]["node_input_size"] + NodeType.SIZE,
